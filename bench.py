@@ -23,8 +23,13 @@ replay tuples are compacted in HBM and (N>1) all-gathered over RCCL.  value = ga
 during the timed steps / time.  The slots are driven as `--lanes` = 2 independent groups on two streams so
 that one group's trunk launches fill the other's tails and tree phases.
 
-The timed steps run with the engine's HIP-event hooks OFF.  After the timed region one extra PROFILED step
-(hooks on, not part of `value`) measures the dominant kernel live for the roofline object:
+A plain run sets up, warms up, times the K steps and prints the result line (`roofline`, `roofline_rollout`,
+`cpu_baseline` null, no `other_configs`).  `--dump-outputs DIR` also writes what the last timed step returned -- the replay
+tuples of the whole job -- as DIR/states.npy, pis.npy, zs.npy (float32; a fixed seeded sample of the rows when they exceed
+48 MB) and DIR/counts.npy: the workload is seeded, so two builds can be compared output for output.
+
+Everything else runs only with `--full`.  The timed steps run with the engine's HIP-event hooks OFF.  After the timed region
+one extra PROFILED step (hooks on, not part of `value`) measures the dominant kernel live for the roofline object:
   roofline     k_trunk (fused ResNet forward): algorithmic FLOPs (378.03 MFLOP per evaluated position,
                SURVEY 8(d)) / the time during which a trunk launch was running (HIP events on the launch
                streams), against the dense fp16 MFMA peak (2.5 PFLOP/s).
@@ -308,6 +313,37 @@ def proportional_shares(rates, nominal, lanes):
         i += 1
     new[order[0]] += rem   # (only if every rank sits at the upper bound or nominal is not a multiple of the unit)
     return new
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this much tuple data
+
+
+def sample_rows(n, row_bytes, budget=DUMP_BYTES, seed=0):
+    """Rows of an n-row output that --dump-outputs keeps: all of them if they fit the budget, else a fixed (seeded) sorted
+    sample -- the same rows in every run with the same n."""
+    import numpy as np
+    keep = budget // row_bytes
+    if n <= keep:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, torch, tuples, games):
+    """Write the last timed step's return value -- `tuples` = (states, pis, zs), each a list of parts in order (one per lane;
+    one after the exchange of an N > 1 job) -- to dirname/{states,pis,zs}.npy (float32, the rows of sample_rows) and
+    dirname/counts.npy (float64: games this rank finished in the step, tuples of the step, tuples written)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    st, pi, z = (torch.cat([p_.reshape(p_.shape[0], int(np.prod(p_.shape[1:]))) for p_ in parts]) for parts in tuples)
+    n = int(z.shape[0])
+    rows = sample_rows(n, 4 * (st.shape[1] + pi.shape[1] + 1))
+    idx = torch.from_numpy(rows).to(z.device)
+    shape = tuple(tuples[0][0].shape[1:])
+    np.save(os.path.join(dirname, "states.npy"), st.index_select(0, idx).cpu().numpy().astype(np.float32).reshape((-1,) + shape))
+    np.save(os.path.join(dirname, "pis.npy"), pi.index_select(0, idx).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirname, "zs.npy"), z.index_select(0, idx).cpu().numpy().astype(np.float32).reshape(-1))
+    np.save(os.path.join(dirname, "counts.npy"), np.array([games, n, len(rows)], dtype=np.float64))
+    return n, len(rows)
 
 
 def union_ms(spans):
@@ -648,7 +684,17 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=20.0,
                     help="seconds of CPU work for the baseline (every stream plays whole plies until this much time has passed "
                          "and it has played at least 8: ~35 s of wall clock at ~4 s per ply)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what is not part of the headline figure: the profiled step(s) of the "
+                         "roofline objects (--profile-steps), the secondary legs (`other_configs`) and the CPU baseline.  "
+                         "Without it the run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned -- the replay tuples (states, pis, zs) "
+                         "of the whole job -- as DIR/<name>.npy (float32; a fixed, seeded sample of the rows when they exceed "
+                         "%d MB; counts.npy: float64)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline only
+        args.profile_steps, args.no_other_configs, args.no_cpu_baseline = 0, True, True
     rc = check_world(args, sys.argv[1:])
     if rc is not None:
         sys.exit(rc)
@@ -725,6 +771,7 @@ def main():
 
     xchg = {"s": 0.0, "n": 0}   # time of the exchange step inside the timed region (this rank)
     state = {"warming": True}   # warm-up steps may run the lane-overlap check (hooks on); timed steps never do
+    last = {"tuples": None, "games": 0}   # what the last step returned (views, valid until the next step): --dump-outputs
 
     def step():
         """-> (games this rank finished, replay samples of the whole job after the exchange)"""
@@ -740,8 +787,11 @@ def main():
             torch.cuda.synchronize()   # (the collectives are asynchronous: the exchange is timed to its end)
             xchg["s"] += time.time() - t_x
             xchg["n"] += 1
+            last["tuples"] = ([st], [pi], [z])
         else:          # single GPU: the tuples stay where the lanes compacted them (no copy)
             samples = sum(int(p_[2].shape[0]) for p_ in parts)
+            last["tuples"] = tuple([p_[j] for p_ in parts] for j in range(3))
+        last["games"] = games
         rebalance(games, t_play)
         return games, samples
 
@@ -807,6 +857,9 @@ def main():
         dt, total_games = float(tmax[0].item()), int(round(float(t[1].item())))
         exchange_ms = round(float(tmax[2].item()), 3)   # the slowest rank's mean exchange time per timed step
     stats = {k: c1[k] - c0.get(k, 0) for k in c1}
+    if args.dump_outputs and rank == 0 and last["tuples"] is not None:   # before any further step reuses the buffers
+        n_all, n_kept = dump_outputs(args.dump_outputs, torch, last["tuples"], last["games"])
+        beat("outputs of the last timed step: %d of %d tuples written to %s" % (n_kept, n_all, args.dump_outputs))
 
     # ---- profiled step(s) outside the timed region: HIP-event spans of every trunk launch ------------------------
     prof = {"evals": 0, "net_ms": 0.0, "net_launches": 0, "tree_ms": 0.0, "tree_launches": 0, "union_ms": 0.0,
@@ -828,7 +881,9 @@ def main():
     my_overlap = prof["net_ms"] / prof["union_ms"] if prof["union_ms"] > 0 else 0.0
     my_launch_ms = prof["net_ms"] / max(1, prof["net_launches"])
     per_rank_overlap, per_rank_launch_ms = [round(my_overlap, 3)], [round(my_launch_ms, 4)]
-    if use_dist:
+    if not args.full:   # no profiled step ran: nothing was measured
+        per_rank_overlap, per_rank_launch_ms = None, None
+    elif use_dist:
         t = torch.tensor([my_overlap, my_launch_ms], dtype=torch.float64, device="cpu" if gloo else "cuda")
         allo = torch.zeros(2 * world, dtype=torch.float64, device=t.device)
         dist.all_gather_into_tensor(allo, t)
@@ -837,19 +892,20 @@ def main():
         per_rank_launch_ms = [round(float(allo[r, 1]), 4) for r in range(world)]
 
     if rank == 0:
-        # With one lane the union equals the sum of the launch durations; with several lanes the launches of the
-        # lanes overlap on the device, so FLOPs are divided by the time during which the kernel was running at all.
-        net_s = prof["union_ms"] * 1e-3
-        achieved, peak, kinfo = wl.roofline_numbers(prof)
         prec = ev.precision
-        # HBM-side bytes per launch: the committed PMC passes over THIS command's own launch shape (two lanes, ~1 900
-        # positions per trunk launch) -- a file constant, so it says when it no longer describes this build's kernel
-        ct = committed_traffic(kinfo["kernel"])
-        traffic, tree_traffic, traffic_basis = ct["traffic"], ct["tree_traffic"], ct["basis"]
-        # which trunk kernel ran and how many MFMA FLOPs it issues per algorithmic FLOP come from the LIBRARY
-        # (oth_net_kernel_info follows the dispatch of oth_net_forward_bits), not from a re-derivation here
-        issued = kinfo["issued_per_flop"]
-        wide = args.filters == 128 and args.board == 8 and prec != "f32"   # the configuration the PMC traffic file is for
+        if args.full:
+            # With one lane the union equals the sum of the launch durations; with several lanes the launches of the
+            # lanes overlap on the device, so FLOPs are divided by the time during which the kernel was running at all.
+            net_s = prof["union_ms"] * 1e-3
+            achieved, peak, kinfo = wl.roofline_numbers(prof)
+            # HBM-side bytes per launch: the committed PMC passes over THIS command's own launch shape (two lanes, ~1 900
+            # positions per trunk launch) -- a file constant, so it says when it no longer describes this build's kernel
+            ct = committed_traffic(kinfo["kernel"])
+            traffic, tree_traffic, traffic_basis = ct["traffic"], ct["tree_traffic"], ct["basis"]
+            # which trunk kernel ran and how many MFMA FLOPs it issues per algorithmic FLOP come from the LIBRARY
+            # (oth_net_kernel_info follows the dispatch of oth_net_forward_bits), not from a re-derivation here
+            issued = kinfo["issued_per_flop"]
+            wide = args.filters == 128 and args.board == 8 and prec != "f32"   # the configuration the PMC traffic file is for
         evals_per_game = stats["evals"] / max(1, stats["games"])
         out = {
             "metric": "self-play games/sec (%dx%d, %d MCTS sims/move)" % (args.board, args.board, args.sims),
@@ -906,7 +962,7 @@ def main():
                 "plies_per_game": round(stats["plies"] / max(1, stats["games"]), 2),
                 "timing_hooks_in_timed_region": bool(args.hooks_always),
             },
-            "roofline": {
+            "roofline": None if not args.full else {
                 "kernel": kinfo["kernel"],
                 "bound": "mfma",
                 "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
@@ -942,7 +998,7 @@ def main():
             },
             "cpu_baseline": None,
         }
-        if wide and ct["stale"]:
+        if args.full and wide and ct["stale"]:
             print("[bench] WARNING: roofline.traffic is stale (%s): re-run tools/bench_pmc.sh and commit its JSON under profiles/"
                   % ct["why"], file=sys.stderr, flush=True)
         # the rollout (tree search) kernel against the HBM roofline: algorithmic bytes of one launch (one simulation of
@@ -950,7 +1006,7 @@ def main():
         tree_us = prof["tree_ms"] * 1e3 / max(1, prof["tree_launches"])
         tree_bytes = TREE_BYTES_PER_GAME_SIM * (args.games // lanes)
         tree_gbs = tree_bytes / (tree_us * 1e-6) / 1e9 if tree_us > 0 else 0.0
-        out["roofline_rollout"] = {
+        out["roofline_rollout"] = None if not args.full else {
             "kernel": "k_tree (expand + backup of the evaluated leaf, next PUCT descent or ply step; one launch per "
                       "simulation and lane)",
             "bound": "hbm", "achieved": round(tree_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
@@ -963,7 +1019,8 @@ def main():
                     "bound); it runs concurrently with the other lane's trunk launch",
         }
         # evidence first: if the CPU leg were to be killed the measured line is already on stderr
-        print("[bench partial] " + json.dumps(out), file=sys.stderr, flush=True)
+        if args.full:
+            print("[bench partial] " + json.dumps(out), file=sys.stderr, flush=True)
         # ---- short secondary legs: the other single-GPU BASELINE configurations, driver-run in the same process --------
         headline = (args.board, args.blocks, args.filters, args.sims, args.games, args.eval_cache, args.precision) == \
             (8, 10, 128, 50, 4096, 0, None)

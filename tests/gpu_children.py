@@ -26,7 +26,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REHEARSAL_RANKS = 4
 SMALL = ["--steps", "2", "--warmup", "1", "--games", "64", "--step-games", "32", "--sims", "6", "--blocks", "2",
-         "--filters", "16", "--stagger", "8", "--profile-steps", "1", "--no-cpu-baseline", "--no-other-configs"]
+         "--filters", "16", "--stagger", "8", "--full", "--profile-steps", "1", "--no-cpu-baseline", "--no-other-configs"]
 
 
 def free_port():

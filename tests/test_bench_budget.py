@@ -1,4 +1,4 @@
-"""bench.py must finish inside the driver's limit: `python bench.py --gpus 1 --steps 20 --warmup 5` gets 600 s on
+"""bench.py must finish inside the driver's limit: `python bench.py --gpus 1 --steps 20 --warmup 5 --full` gets 600 s on
 a fresh box (first `import torch` included).  Round 1's bench was killed at that limit with nothing printed, so the
 step size is now planned against a conservative rate and this test fails if the plan no longer fits."""
 import importlib.util
@@ -138,3 +138,28 @@ def test_cpu_baseline_estimator_weights_by_game_phase():
     # an empty phase bin is filled from its neighbours
     spg = b.seconds_per_game(np.array([0, 1, 2, 30, 31, 58, 59]), np.array([4.0, 4, 4, 4, 4, 1, 1]))
     assert 4.0 * 30 < spg < 4.0 * 60.7
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs: float32 .npy files of the last step's tuples (the lanes' parts in order); more rows than the budget holds
+    -> a sorted sample that depends on the row count alone, so two runs of the same workload keep the same rows."""
+    import numpy as np
+    import torch
+    b = _bench()
+    assert b.DUMP_BYTES <= 64 << 20
+    rows = b.sample_rows(1000, 1032)
+    assert np.array_equal(rows, np.arange(1000))
+    n = 3 * (b.DUMP_BYTES // 1032)
+    rows = b.sample_rows(n, 1032)
+    assert len(rows) == b.DUMP_BYTES // 1032 and len(rows) * 1032 <= b.DUMP_BYTES
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(rows, b.sample_rows(n, 1032)) and not np.array_equal(rows, b.sample_rows(n + 1, 1032))
+    g = torch.Generator().manual_seed(1)
+    parts = [(torch.rand(m, 3, 8, 8, generator=g), torch.rand(m, 65, generator=g), torch.rand(m, generator=g)) for m in (5, 0, 7)]
+    tuples = tuple([p[j] for p in parts] for j in range(3))
+    assert b.dump_outputs(str(tmp_path / "d"), torch, tuples, 2) == (12, 12)
+    st, pi, z, cnt = (np.load(tmp_path / "d" / (k + ".npy")) for k in ("states", "pis", "zs", "counts"))
+    assert st.dtype == pi.dtype == z.dtype == np.float32 and cnt.dtype == np.float64 and cnt.tolist() == [2.0, 12.0, 12.0]
+    assert st.shape == (12, 3, 8, 8) and pi.shape == (12, 65) and z.shape == (12,)
+    assert np.array_equal(st[5:], parts[2][0].numpy()) and np.array_equal(pi[:5], parts[0][1].numpy())
+    assert np.array_equal(z, torch.cat([p[2] for p in parts]).numpy())

@@ -116,3 +116,41 @@ def test_bench_other_configs_leg_small():
     assert 0 < b["eval_cache"]["hit_rate"] < 1 and "c_puct 1.50" in b["workload"] and "threshold 20" in b["workload"]
     ec = b["eval_cache"]   # the misses split into first evaluations and repeats; evictions counted
     assert ec["compulsory_misses"] > 0 and ec["compulsory_misses"] + ec["repeat_misses"] > 0 and ec["conflict_evictions"] >= 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_identical_outputs(tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) at toy size, in this process: the result line carries the headline keys and none of the figures
+    that need runs of their own, and --dump-outputs writes the last timed step's tuples -- identical from run to run."""
+    import importlib.util
+    import os
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OTHELLO_FORCE_DIST"):
+        monkeypatch.delenv(k, raising=False)
+    outs = []
+    for name in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--games", "64", "--step-games", "32",
+                                          "--sims", "6", "--blocks", "2", "--filters", "16", "--stagger", "8",
+                                          "--dump-outputs", str(tmp_path / name)])
+        bench.main()
+        cap = capsys.readouterr()
+        d = _json_line(cap.out)
+        assert "step 3/3" in cap.err and "step 4/3" not in cap.err and "profiled step" not in cap.err
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "games/s"
+        assert d["higher_is_better"] is True and d["dtype"].startswith("f32") and "8x8, 6 MCTS sims" in d["metric"]
+        assert abs(d["ms_per_step"] * 3e-3 * d["value"] - d["config"]["games_timed"]) < 0.01 * d["config"]["games_timed"]
+        assert d["roofline"] is None and d["roofline_rollout"] is None and d["cpu_baseline"] is None and "other_configs" not in d
+        arr = {k: np.load(tmp_path / name / (k + ".npy")) for k in ("states", "pis", "zs", "counts")}
+        games, n, kept = (int(v) for v in arr["counts"])
+        assert games >= 32 and n == kept == d["config"]["samples_last_step"] and n > games * 20
+        assert arr["states"].shape == (n, 3, 8, 8) and arr["pis"].shape == (n, 65) and arr["zs"].shape == (n,)
+        assert all(arr[k].dtype == np.float32 for k in ("states", "pis", "zs"))
+        assert np.allclose(arr["pis"].sum(1), 1.0, atol=1e-5) and set(np.unique(arr["zs"])) <= {-1.0, 0.0, 1.0}
+        assert set(np.unique(arr["states"])) <= {0.0, 1.0}
+        outs.append(arr)
+    assert all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])

@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-CMD="python3 bench.py --gpus 1 --steps 1 --warmup 2 --step-games 512 --stagger 8 --profile-steps 1 --no-cpu-baseline --no-other-configs"
+CMD="python3 bench.py --gpus 1 --full --steps 1 --warmup 2 --step-games 512 --stagger 8 --profile-steps 1 --no-cpu-baseline --no-other-configs"
 out=gpurun_out/pmc_bench
 rm -rf "$out"; mkdir -p "$out"
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum"; do

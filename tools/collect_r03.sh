@@ -7,11 +7,11 @@ O=gpurun_out/r03; mkdir -p $O
 parts=${@:-driver stats pmc nets configs small exact}
 for part in $parts; do case $part in
 driver)   # the driver's own command, verbatim
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.stderr.txt
+  python3 bench.py --gpus 1 --full --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.stderr.txt
   tail -c 600 $O/bench_driver_cmd.json | head -c 300; echo ;;
 stats)    # rocprofv3 --kernel-trace --stats of bench.py with the hooks on everywhere (same launches timed by both)
   rm -rf /tmp/prof_r03
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_r03 -o x -- python3 bench.py --gpus 1 --steps 3 --warmup 2 --hooks-always --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+  rocprofv3 --kernel-trace --stats -d /tmp/prof_r03 -o x -- python3 bench.py --gpus 1 --full --steps 3 --warmup 2 --hooks-always --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
   db=$(find /tmp/prof_r03 -name "*.db" | head -1)
   python3 tools/rocpd_stats.py "$db" > $O/bench_kernel_stats.csv; head -4 $O/bench_kernel_stats.csv | cut -c1-150; rm -rf /tmp/prof_r03 ;;
 pmc)

@@ -2,7 +2,7 @@
 # The reference's configurations (and BASELINE.json configs[3], configs[4]) on the streaming engine, one MI355X.
 # usage (GPU box, repo root): bash tools/configs_table.sh > gpurun_out/configs_table.jsonl
 set -e
-B="python3 bench.py --gpus 1 --no-cpu-baseline"
+B="python3 bench.py --gpus 1 --full --no-cpu-baseline"
 $B --sims 15 --steps 4 --warmup 2 --step-games 4096                       # fast_8x8: 15 sims, 10x128
 $B --sims 15 --blocks 6 --steps 4 --warmup 2 --step-games 4096            # ultrafast_8x8: 15 sims, 6x128
 $B --sims 25 --steps 4 --warmup 2 --step-games 2048                       # default_8x8: 25 sims, 10x128
