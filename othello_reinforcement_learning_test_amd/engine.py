@@ -23,8 +23,9 @@ _PROBE = {}   # board size -> (self, opp, legal) uint64 arrays
 
 def probe_positions(board_size=8, n=256):
     """A fixed set of n positions of seeded random games (its own numpy Generator: the global RNG the workers draw their seeds
-    from is not touched), played with the library's host rules: what HipResNetEvaluator.refresh() evaluates once after a weight
-    update to choose the activation scale as a function of the WEIGHTS (see refresh)."""
+    from is not touched), played with the library's host rules: what HipResNetEvaluator evaluates once after a weight
+    update (refresh) and, built with calibrate=True, at construction to choose the activation scale as a function of the
+    WEIGHTS (see refresh)."""
     got = _PROBE.get((board_size, n))
     if got is None:
         lib = _lib.load()
@@ -50,9 +51,16 @@ class HipResNetEvaluator:
     OthelloResNet or net.OthelloResNet).  The trainer keeps updating that module between
     ``execute_episodes`` calls (SURVEY 8(b) threading note), so ``refresh()`` re-reads the weights
     whenever a parameter/buffer version counter has moved.
+
+    ``calibrate=True``: the constructor also runs the probe launch that refresh() runs after every weight update (one launch
+    of 256 positions, ``calibrate``), so that an evaluator BUILT on weights W and one UPDATED to W run W at the same activation
+    scale and return the same bits; a rescue it triggers is recorded in ``rescues`` and warned about like any other.  The
+    workers and search mirrors of this package (BatchMCTS, MCTS -- everything a trainer reaches) construct their evaluators
+    this way.  The default is off: a bare evaluator starts at scale 16 whatever its weights, launches nothing and warns about
+    nothing until it is used (what callers that set the scale themselves, bench.py and the rescue tests build on).
     """
 
-    def __init__(self, model, precision=None):
+    def __init__(self, model, precision=None, calibrate=False):
         _lib.require_device()
         self.model = model
         self.num_blocks = int(getattr(model, "num_blocks", len(model.res_blocks)))
@@ -71,6 +79,8 @@ class HipResNetEvaluator:
         # rescue of a saturated launch (see needs_rescue): how often it happened, and what was done about it
         self.rescues = []
         self.refresh()
+        if calibrate and self.precision != "f32":
+            self.calibrate()
 
     def _model_version(self):
         v = 0
@@ -86,8 +96,11 @@ class HipResNetEvaluator:
         so results depended on the process's history): both go back to their starting values (16, the constructor's
         precision), the new weights are uploaded, and ONE launch over a fixed set of 256 probe positions (probe_positions)
         lets the rescue lower the scale again if these weights need it -- so the scale a call runs at is a function of the
-        weights (and, only if a position outside the probe set saturates later, of that call).  No launch of this network
-        may be in flight (the workers call refresh() at the start of a call)."""
+        weights (and, only if a position outside the probe set saturates later, of that call).  The constructor's own upload
+        runs the same probe launch when the evaluator is built with ``calibrate=True`` (the workers do: ADVICE r6 item 3 --
+        they used to start at 16 whatever the weights, and ran a checkpoint they were built on at another scale, with other
+        low bits, than one they were updated to); a bare evaluator starts at 16.  No launch of this network may be in flight
+        (the workers call refresh() at the start of a call)."""
         ver = self._model_version()
         moved = self._version is not None and ver != self._version
         if force or ver != self._version:

@@ -41,7 +41,7 @@ class MCTS:
         self.c_puct = c_puct
         self.dirichlet_alpha = dirichlet_alpha
         self.dirichlet_epsilon = dirichlet_epsilon
-        self.evaluator = HipResNetEvaluator(model, precision=precision)
+        self.evaluator = HipResNetEvaluator(model, precision=precision, calibrate=True)
         self._engines = {}
 
     def _engine(self, num_simulations, max_games=1):

@@ -31,7 +31,7 @@ class BatchMCTS:
         # evaluator: a HipResNetEvaluator (default: built from `model`), or any object with
         # host_eval(self u64[m], opp u64[m], legal u64[m]) -> (probs f32[m,65], values f32[m]) -- an external
         # evaluator driven through oth_search_leaves / oth_search_expand (stub evaluators of the parity tests)
-        self.evaluator = evaluator or HipResNetEvaluator(model, precision=precision)
+        self.evaluator = evaluator or HipResNetEvaluator(model, precision=precision, calibrate=True)
         self._external = hasattr(self.evaluator, "host_eval")
         self._engines = {}
 
