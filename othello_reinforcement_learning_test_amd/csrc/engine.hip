@@ -1129,7 +1129,9 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
     r |= dev_alloc(e, &e->r_visits, (size_t)G * 65); r |= dev_alloc(e, &e->r_wsum, (size_t)G * 65);
     r |= dev_alloc(e, &e->r_act, G);
     if (cfg->eval_cache_log2 > 0) {
-        const int lg = cfg->eval_cache_log2 < 10 ? 10 : (cfg->eval_cache_log2 > 26 ? 26 : cfg->eval_cache_log2);
+        // 2^n entries as the header says, down to n = 1 (one set of two ways; a request below 10 used to be raised to 10
+        // silently, so a table small enough to evict at nearly every insert could not be asked for); 26 is the ceiling
+        const int lg = cfg->eval_cache_log2 > 26 ? 26 : cfg->eval_cache_log2;
         const size_t C = (size_t)1 << lg;
         r |= dev_alloc(e, &d.ck, C * 2);
         r |= dev_alloc(e, &d.cv, C * 66);
