@@ -99,7 +99,8 @@ int oth_rules_checksum_n(int board_size, int64_t n, uint64_t *legal_acc /*HOST*/
  * 3. Evaluator: OthelloResNet forward (src/model/net.py:139-205), eval mode
  * =========================================================================================== */
 typedef struct oth_net oth_net;
-#define OTH_PREC_F32 0     /* exact fp32 on the matrix cores (v_mfma_f32_16x16x4_f32): 16/32/64/128 filters, 8x8 and 6x6 */
+#define OTH_PREC_F32 0     /* exact fp32 on the matrix cores (v_mfma_f32_16x16x4_f32): every multiple of 16 from 16 to 256
+                              filters, 8x8 and 6x6 */
 #define OTH_PREC_F16X3 1   /* MFMA, fp16 hi/lo split of both operands, fp32 accumulate (fp32-equivalent): 32 / 64 / 128
                               filters on 8x8 and 6x6 */
 #define OTH_PREC_F16 2     /* MFMA, single fp16 pass (fast; NOT within the 1e-4 parity tolerance in general); 128 filters, 8x8 */
@@ -109,8 +110,12 @@ typedef struct oth_net oth_net;
                                  * summation) */
 
 /* net.py:157-180 __init__(num_blocks, num_filters, board_size).  board_size 8 or 6 (configs/debug_6x6.yaml);
- * num_filters 16, 32, 64 or 128.  A 6x6 network takes positions as bit i = row*6 + col (i < 36) and returns
- * 37 log-probabilities per position. */
+ * num_filters any multiple of 16 from 16 to 256 (anything else: NULL and a message stating this rule).  At
+ * OTH_PREC_F32 every such width runs on both boards: up to 128 filters k_trunk_f32 (one wave carries a position group),
+ * 144 to 256 k_trunk_f32c (the waves of a workgroup share the position group's planes and split the output channels);
+ * OTH_F32_COOP=1 in the environment, read per launch, routes 64 and 128 filters to k_trunk_f32c as well -- the A/B
+ * switch, bit-identical outputs.  The fp16-split precisions exist for 32 / 64 / 128 filters only.  A 6x6 network takes
+ * positions as bit i = row*6 + col (i < 36) and returns 37 log-probabilities per position. */
 oth_net *oth_net_create(int num_blocks, int num_filters, int board_size);
 /* board_size^2 + 1: length of a policy row of this network (65 or 37) */
 int oth_net_policy_size(const oth_net *net);

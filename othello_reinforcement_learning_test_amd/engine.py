@@ -12,7 +12,9 @@ from . import _lib
 def default_precision(num_filters, board_size=8):
     """fp16-split MFMA trunks (fp32-equivalent: three f16 products per operand pair) where one exists -- 128 filters on
     8x8 (k_trunk16, the benchmarked kernel), 32 / 64 filters on 8x8 and 6x6 and 128 filters on 6x6 (k_trunk_h3) -- else
-    the exact-fp32 MFMA trunk (16 filters)."""
+    the exact-fp32 MFMA trunks: 16 filters and every other multiple of 16 up to 256 (48, 80, 96, 112: k_trunk_f32;
+    144 to 256: the workgroup-cooperative k_trunk_f32c -- no fp16-split kernel exists for these widths, and
+    precision="f16x3" on them is refused)."""
     if num_filters == 128:
         return "f16x3"     # 8x8: k_trunk16; 6x6: k_trunk_h3
     return "f16x3" if num_filters in (32, 64) else "f32"
