@@ -95,6 +95,35 @@ int oth_tensor_input_batch_n(int board_size, const uint64_t *self_b, const uint6
                              void *stream);
 int oth_rules_checksum_n(int board_size, int64_t n, uint64_t *legal_acc /*HOST*/, uint64_t *flip_acc /*HOST*/, void *stream);
 
+/* ---- rule sets ----------------------------------------------------------------------------------------------------
+ * OTH_RULES_REFERENCE is the game every function above plays: the reference's, whose A/H-file masks are swapped and
+ * applied after the shift (bitboard.pyx:29-38), so that horizontal and diagonal rays stop one file early and wrap across
+ * the board edge.  Bit-exact parity with that is this library's contract and the default everywhere.
+ * OTH_RULES_OTHELLO is standard Othello: the post-shift masks are the unswapped ones (directions -1, -(N+1), +(N-1) clear
+ * column N-1, directions +1, -(N-1), +(N+1) clear column 0, +-N stay unmasked), everything else -- start position, pass
+ * action N*N, make_move, is_terminal, winner -- is unchanged.  It has no counterpart in the reference; it is pinned by an
+ * independent row/column ray walk and by the published perft series (4, 12, 56, 244, 1396, 8200, 55092, 390216).
+ * The `_r` forms take board_size = 8 or 6 and rules = one of the two values; with OTH_RULES_REFERENCE they are the `_n`
+ * forms.  An unknown board size or rule set is an error: the status-returning functions return OTH_E_INVALID, the
+ * value-returning ones (legal_moves, flip_bits, make_move, is_terminal) return 0, and oth_last_error() names the argument. */
+#define OTH_RULES_REFERENCE 0
+#define OTH_RULES_OTHELLO 1
+int oth_board_reset_r(int board_size, int rules, oth_board *b);
+uint64_t oth_legal_moves_r(int board_size, int rules, uint64_t self_board, uint64_t opp_board);
+uint64_t oth_flip_bits_r(int board_size, int rules, int pos, uint64_t self_board, uint64_t opp_board);
+int oth_board_make_move_r(int board_size, int rules, oth_board *b, int pos);
+int oth_board_is_terminal_r(int board_size, int rules, const oth_board *b);
+int oth_legal_moves_batch_r(int board_size, int rules, const uint64_t *self_b, const uint64_t *opp_b, uint64_t *legal,
+                            int64_t n, void *stream);
+int oth_make_move_batch_r(int board_size, int rules, uint64_t *self_b, uint64_t *opp_b, const int32_t *pos, int32_t *ok,
+                          uint64_t *flips, int64_t n, void *stream);
+int oth_status_batch_r(int board_size, int rules, const uint64_t *self_b, const uint64_t *opp_b, int32_t *terminal,
+                       int32_t *winner, int64_t n, void *stream);
+int oth_tensor_input_batch_r(int board_size, int rules, const uint64_t *self_b, const uint64_t *opp_b, float *out,
+                             int64_t n, void *stream);
+int oth_rules_checksum_r(int board_size, int rules, int64_t n, uint64_t *legal_acc /*HOST*/, uint64_t *flip_acc /*HOST*/,
+                         void *stream);
+
 /* =============================================================================================
  * 3. Evaluator: OthelloResNet forward (src/model/net.py:139-205), eval mode
  * =========================================================================================== */
@@ -192,6 +221,10 @@ typedef struct {
                                   [.,3,8,8] array [.,3,6,6]; rules as oth_*_n(6, ...) define them -- PARITY
                                   UNPINNED, the reference has no 6x6 rules.  The network given to
                                   oth_engine_set_net must have been created for the same board size. */
+    int32_t rules;             /* OTH_RULES_REFERENCE (0): the reference's game, today's behaviour bit for bit.
+                                  OTH_RULES_OTHELLO (1): every rules call of the search and of self-play (legal moves,
+                                  flips, end of game) follows standard Othello; the search semantics, the RNG, the cache
+                                  and the tuple layout are the same.  Any other value: oth_engine_create fails. */
 } oth_engine_cfg;
 
 oth_engine *oth_engine_create(const oth_engine_cfg *cfg);

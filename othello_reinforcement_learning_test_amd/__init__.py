@@ -2,6 +2,7 @@
 
 Drop-in surface (reference module -> here):
   src.cython.bitboard.OthelloBitboard            -> bitboard.OthelloBitboard
+  (no counterpart: standard Othello rules)       -> bitboard.StandardOthelloBitboard (opt-in; `game.rules: othello`)
   src.mcts.mcts.MCTS                             -> mcts.MCTS
   src.mcts.node.MCTSNode                         -> node.MCTSNode (host object view; the engine's trees are device arrays)
   src.train.self_play.SelfPlayWorker             -> self_play.SelfPlayWorker
@@ -19,7 +20,7 @@ MI355X raises OthelloHipError.  There is no CPU fallback.
 from ._lib import OthelloHipError, device_available  # noqa: F401
 from .arena import (Arena, BatchedArena, GreedyPlayer, MatchResult, MCTSPlayer, Player,  # noqa: F401
                     RandomPlayer, evaluate_player)
-from .bitboard import DeviceBoards, OthelloBitboard  # noqa: F401
+from .bitboard import DeviceBoards, OthelloBitboard, StandardOthelloBitboard  # noqa: F401
 from .engine import HipResNetEvaluator, SearchEngine  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .node import MCTSNode  # noqa: F401
@@ -31,7 +32,7 @@ from .replay import (DeviceReplayBuffer, augment_symmetries, augment_training_da
 from .self_play import GameStep, SelfPlayWorker, augment_data_with_symmetries  # noqa: F401
 
 __all__ = [
-    "OthelloBitboard", "DeviceBoards", "MCTS", "MCTSNode", "BatchMCTS", "SelfPlayWorker", "ParallelSelfPlayWorker",
+    "OthelloBitboard", "StandardOthelloBitboard", "DeviceBoards", "MCTS", "MCTSNode", "BatchMCTS", "SelfPlayWorker", "ParallelSelfPlayWorker",
     "create_parallel_self_play_worker", "GameStep", "augment_data_with_symmetries", "OthelloResNet",
     "create_model", "HipResNetEvaluator", "SearchEngine", "OthelloHipError", "device_available",
     "DeviceReplayBuffer", "augment_symmetries", "augment_training_data", "load_checkpoint_model",

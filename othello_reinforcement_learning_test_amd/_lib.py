@@ -46,6 +46,33 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OTHELLO_MI355X_LIB") or os.path.join(_HERE, "libothello_mi355x.so")
 
 OTH_PREC_F32, OTH_PREC_F16X3, OTH_PREC_F16, OTH_PREC_F16X3_DIRECT = 0, 1, 2, 3
+# rule sets (OTH_RULES_* of the header): "reference" = the reference's game, the default everywhere; "othello" = standard Othello
+OTH_RULES_REFERENCE, OTH_RULES_OTHELLO = 0, 1
+RULES = {"reference": OTH_RULES_REFERENCE, "othello": OTH_RULES_OTHELLO}
+
+
+def rules_id(rules):
+    """"reference" / "othello" (or 0 / 1) -> the OTH_RULES_* value; anything else is a ValueError."""
+    if isinstance(rules, str) and rules in RULES:
+        return RULES[rules]
+    if not isinstance(rules, (str, bool)) and rules in (OTH_RULES_REFERENCE, OTH_RULES_OTHELLO):
+        return int(rules)
+    raise ValueError("rules must be one of %s, got %r" % (sorted(RULES), rules))
+
+
+def rules_name(rules):
+    return "othello" if rules_id(rules) == OTH_RULES_OTHELLO else "reference"
+
+
+def common_rules(boards, expected=None):
+    """The one rule set of a list of board objects (their class attribute ``rules``; objects without one play the
+    reference's game).  A mix -- among the boards, or with `expected` -- is refused with a ValueError."""
+    names = {rules_name(getattr(b, "rules", "reference")) for b in boards}
+    if expected is not None:
+        names.add(rules_name(expected))
+    if len(names) > 1:
+        raise ValueError("boards of different rule sets in one call: %s" % sorted(names))
+    return names.pop() if names else "reference"
 # "f16x3": the default for 32 / 64 / 128 filters (128 on 8x8: the 1-D Winograd trunk); "f16x3_direct": the same arithmetic
 # on the direct-convolution kernel (128 filters on 8x8 only)
 PRECISIONS = {"f32": OTH_PREC_F32, "f16x3": OTH_PREC_F16X3, "f16": OTH_PREC_F16, "f16x3_direct": OTH_PREC_F16X3_DIRECT}
@@ -64,7 +91,8 @@ class EngineCfg(C.Structure):  # oth_engine_cfg
     _fields_ = [("max_games", C.c_int32), ("num_simulations", C.c_int32),
                 ("temperature_threshold", C.c_int32), ("c_puct", C.c_float),
                 ("dirichlet_alpha", C.c_double), ("dirichlet_epsilon", C.c_double),
-                ("store_late_onehot", C.c_int32), ("eval_cache_log2", C.c_int32), ("board_size", C.c_int32)]
+                ("store_late_onehot", C.c_int32), ("eval_cache_log2", C.c_int32), ("board_size", C.c_int32),
+                ("rules", C.c_int32)]
 
 
 u64p, f32p, i32p, f64p, i64p = (C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
@@ -99,6 +127,16 @@ _SIGS = {
     "oth_status_batch_n": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
     "oth_tensor_input_batch_n": (C.c_int, [C.c_int, vp, vp, vp, C.c_int64, vp]),
     "oth_rules_checksum_n": (C.c_int, [C.c_int, C.c_int64, u64p, u64p, vp]),
+    "oth_board_reset_r": (C.c_int, [C.c_int, C.c_int, C.POINTER(Board)]),
+    "oth_legal_moves_r": (C.c_uint64, [C.c_int, C.c_int, C.c_uint64, C.c_uint64]),
+    "oth_flip_bits_r": (C.c_uint64, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64]),
+    "oth_board_make_move_r": (C.c_int, [C.c_int, C.c_int, C.POINTER(Board), C.c_int]),
+    "oth_board_is_terminal_r": (C.c_int, [C.c_int, C.c_int, C.POINTER(Board)]),
+    "oth_legal_moves_batch_r": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp]),
+    "oth_make_move_batch_r": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, vp]),
+    "oth_status_batch_r": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+    "oth_tensor_input_batch_r": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp]),
+    "oth_rules_checksum_r": (C.c_int, [C.c_int, C.c_int, C.c_int64, u64p, u64p, vp]),
     "oth_net_create": (vp, [C.c_int, C.c_int, C.c_int]),
     "oth_net_destroy": (None, [vp]),
     "oth_net_state_floats": (C.c_int64, [vp]),
@@ -142,7 +180,8 @@ _SIGS = {
     "oth_replay_gather_n": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]),
     "oth_augment_symmetries_n": (C.c_int, [C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, vp]),
 }
-_PLAIN_INT = {"oth_device_available", "oth_net_policy_size", "oth_board_make_move_n", "oth_board_is_terminal_n", "oth_board_make_move", "oth_board_is_terminal", "oth_board_get_winner"}
+_PLAIN_INT = {"oth_device_available", "oth_net_policy_size", "oth_board_make_move_n", "oth_board_is_terminal_n",
+              "oth_board_make_move_r", "oth_board_is_terminal_r", "oth_board_make_move", "oth_board_is_terminal", "oth_board_get_winner"}
 
 _lib = None
 

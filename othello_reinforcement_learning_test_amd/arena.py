@@ -129,11 +129,12 @@ def _result_from_final_board(board, p1_name, p2_name, starting_player, duration)
 class Arena:
     """arena.py:55-232"""
 
-    def __init__(self, verbose=True):
+    def __init__(self, verbose=True, board_class=OthelloBitboard):
         self.verbose = verbose
+        self.board_class = board_class   # StandardOthelloBitboard: the matches are standard Othello (MCTSPlayer follows the board)
 
     def play_game(self, player1, player2, starting_player=1):
-        board = OthelloBitboard()
+        board = self.board_class()
         board.reset()
         player1.reset()
         player2.reset()
@@ -186,9 +187,9 @@ def summarize(results, num_games):
     }
 
 
-def evaluate_player(player, opponent, num_games=10, verbose=True):
+def evaluate_player(player, opponent, num_games=10, verbose=True, board_class=OthelloBitboard):
     """arena.py:235-275"""
-    return summarize(Arena(verbose=verbose).play_matches(player, opponent, num_games=num_games), num_games)
+    return summarize(Arena(verbose=verbose, board_class=board_class).play_matches(player, opponent, num_games=num_games), num_games)
 
 
 class BatchedArena:
@@ -197,12 +198,13 @@ class BatchedArena:
     on the host game by game, in game order (so a seeded RandomPlayer consumes python's RNG deterministically).
     For deterministic opponents the results equal ``Arena.play_matches`` game for game."""
 
-    def __init__(self, batch_mcts, num_simulations=50):
+    def __init__(self, batch_mcts, num_simulations=50, board_class=OthelloBitboard):
         self.batch_mcts = batch_mcts          # parallel_self_play.BatchMCTS
         self.num_simulations = num_simulations
+        self.board_class = board_class        # the searches follow the boards' rule set
 
     def play_matches(self, player1_name, opponent, num_games=10, alternate_colors=True):
-        boards = [OthelloBitboard() for _ in range(num_games)]
+        boards = [self.board_class() for _ in range(num_games)]
         starts = [(1 if g % 2 == 0 else -1) if alternate_colors else 1 for g in range(num_games)]
         t0 = time.time()
         done = [False] * num_games

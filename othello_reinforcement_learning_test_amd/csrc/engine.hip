@@ -354,7 +354,7 @@ __device__ __forceinline__ void begin_root(const Dev& d, int g, uint64_t sb, uin
     }
 }
 
-template <int BS>
+template <int BS, int R>
 __global__ __launch_bounds__(256) void k_search_begin(Dev d, const uint64_t* __restrict__ sb,
                                                       const uint64_t* __restrict__ ob, int n) {
     __shared__ BlockTally bt;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void k_search_begin(Dev d, const uint64_t* __r
         return;
     }
     if (lane == 0) { d.g_active[g] = 1; d.g_self[g] = s0; d.g_opp[g] = o0; }
-    begin_root(d, g, s0, o0, legal_moves_n<BS>(s0, o0), slot, lane);
+    begin_root(d, g, s0, o0, legal_moves_n<BS, R>(s0, o0), slot, lane);
 }
 
 // all slots idle; slot g < n_start joins (starts game id g) at round g * stagger / n_start (stagger 0: at once)
@@ -396,7 +396,8 @@ __global__ void k_slots_init(Dev d, int n_start, int stagger) {
 //                       the end of the game, refill the slot, queue the next root; idle slots whose join round
 //                       has come start their first game;
 //          TREE_NONE    nothing (last launch of a stand-alone search).
-template <int MODE, int BS>
+// R = rule set (othello_rules.h): only the post-shift masks inside the rules calls differ between the instantiations.
+template <int MODE, int BS, int R>
 __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ policy, const float* __restrict__ value,
                                               int is_log, const int32_t* __restrict__ forced, int refill) {
     constexpr int CELLS = Geo<BS>::CELLS;
@@ -453,13 +454,13 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                 const int ce = __shfl(ei, L), child = __shfl(e_child, L), nvis = __shfl(e_n, L);
                 if (lane == 0) lpath[depth] = (uint32_t)ce;
                 ++depth;
-                apply_known_n<BS>(sb, ob, action);  // board.make_move(action), parallel_self_play.py:189
+                apply_known_n<BS, R>(sb, ob, action);  // board.make_move(action), parallel_self_play.py:189
                 if (child == 0) break;        // that child has no children yet: leaf
                 pv = nvis;
                 node = child;
             }
-            lg = legal_moves_n<BS>(sb, ob);
-            terminal = lg == 0 && legal_moves_n<BS>(ob, sb) == 0;  // bitboard.pyx:249-264
+            lg = legal_moves_n<BS, R>(sb, ob);
+            terminal = lg == 0 && legal_moves_n<BS, R>(ob, sb) == 0;  // bitboard.pyx:249-264
             if (!terminal) cached = cache_fetch(d, g, sb, ob, lane);
             need = !terminal && !cached;
         }
@@ -540,9 +541,9 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                     d.hist_bits[h * 3 + 2] = root.legal;
                 }
             }
-            apply_known_n<BS>(sb, ob, action);  // game.board.make_move(action)
+            apply_known_n<BS, R>(sb, ob, action);  // game.board.make_move(action)
             nply = ply + 1;
-            over = is_terminal_n<BS>(sb, ob) || nply >= kMaxPly;
+            over = is_terminal_n<BS, R>(sb, ob) || nply >= kMaxPly;
             if (over) {
                 int new_id = -1;
                 if (lane == 0) {
@@ -587,7 +588,7 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
         if (cached) slot = kCachedSlot;
         if (next_root) {
             if (lane == 0) { d.g_id[g] = gid; d.g_self[g] = sb; d.g_opp[g] = ob; d.g_ply[g] = nply; }
-            begin_root(d, g, sb, ob, legal_moves_n<BS>(sb, ob), slot, lane);
+            begin_root(d, g, sb, ob, legal_moves_n<BS, R>(sb, ob), slot, lane);
         } else if (lane == 0) {
             d.g_active[g] = 0;
             d.g_id[g] = -1;
@@ -730,6 +731,7 @@ struct oth_engine {
     int64_t* d_total = nullptr;
     int device = 0;   // HIP device of every allocation of this engine
     int board = 8;    // board size: 8 (the reference's game) or 6
+    int rules = kRulesReference;   // rule set of every rules call of this engine's kernels (cfg.rules)
     int cells() const { return board * board; }
     int npol() const { return board * board + 1; }
     int32_t n_roots = 0;
@@ -778,6 +780,19 @@ static inline int blocks_for(int n_slots) { return (n_slots + 3) / 4; }
             constexpr int BS = 8;            \
             __VA_ARGS__;                     \
         }                                    \
+    } while (0)
+
+// the same with the rule set as a second constant R, for the kernels that call the rules (k_search_begin, k_tree); the
+// kernels that only move rows of a position's size around (k_cache_insert, k_results, k_compact) stay on OTH_DISPATCH_BS
+#define OTH_DISPATCH_BSR(e, ...)                                      \
+    do {                                                              \
+        if ((e)->rules == kRulesOthello) {                            \
+            constexpr int R = kRulesOthello;                          \
+            OTH_DISPATCH_BS(e, __VA_ARGS__);                          \
+        } else {                                                      \
+            constexpr int R = kRulesReference;                        \
+            OTH_DISPATCH_BS(e, __VA_ARGS__);                          \
+        }                                                             \
     } while (0)
 
 template <typename T>
@@ -888,13 +903,13 @@ static int launch_tree(oth_engine* e, int mode, int is_log, const int32_t* force
     const dim3 grid(blocks_for(e->d.n_slots)), block(256);
     const size_t lds = sizeof(uint32_t) * 4 * e->d.cap_path;
     if (mode == TREE_SELECT)
-        OTH_DISPATCH_BS(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS>), grid, block, lds, s, e->d, e->d.logp, e->d.val,
+        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS, R>), grid, block, lds, s, e->d, e->d.logp, e->d.val,
                                               is_log, forced, refill));
     else if (mode == TREE_PLY)
-        OTH_DISPATCH_BS(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
+        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS, R>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
                                               forced, refill));
     else
-        OTH_DISPATCH_BS(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
+        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS, R>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
                                               forced, refill));
     OTH_HIP(hipGetLastError());
     return span_end(e, s);
@@ -1093,10 +1108,15 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
         set_error("oth_engine_create: board_size must be 8 (or 0 = 8) or 6");
         return nullptr;
     }
+    if (!rules_ok(cfg->rules)) {
+        set_error("oth_engine_create: rules must be OTH_RULES_REFERENCE (0) or OTH_RULES_OTHELLO (1), got %d", (int)cfg->rules);
+        return nullptr;
+    }
     oth_engine* e = new oth_engine();
     e->device = current_device();
     e->cfg = *cfg;
     e->board = cfg->board_size == 6 ? 6 : 8;
+    e->rules = cfg->rules;
     Dev& d = e->d;
     const int G = cfg->max_games, S = cfg->num_simulations;
     d.n_slots = G;
@@ -1206,7 +1226,7 @@ int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int3
     if (rc) return rc;
     if ((rc = cache_clear(e, s))) return rc;
     bind_cursor(e);
-    OTH_DISPATCH_BS(e, hipLaunchKernelGGL((k_search_begin<BS>), dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d,
+    OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_search_begin<BS, R>), dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d,
                                           e->d.g_self, e->d.g_opp, n));
     OTH_HIP(hipGetLastError());
     e->n_roots = n;

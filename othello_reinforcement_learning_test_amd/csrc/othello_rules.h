@@ -5,6 +5,8 @@
 // (SURVEY.md L2): the A/H-file masks are applied AFTER the shift, so the col-1 rays (-1,-9,+7)
 // die on landing in file A and wrap A->H, the col+1 rays (+1,-7,+9) die on landing in file H and
 // wrap H->A; the +-8 rays are plain.  Bit-exact parity with that is the spec, not real Othello.
+// Real Othello is the opt-in second rule set (template parameter R = kRulesOthello below: the unswapped masks, nothing
+// else); R defaults to the reference's rules everywhere.
 //
 // Unlike the reference (one ray walk per empty square, pyx:148-158) legal-move generation here is
 // set-wise: all 64 candidate origins advance together, 6 steps per direction (a ray can hold at
@@ -52,10 +54,21 @@ struct Geo {
     }
     // ... and its mask of pyx:33-38: [ALL, ALL, NOT_A, NOT_H, NOT_A, NOT_H, NOT_A, NOT_H]
     static constexpr uint64_t mask(int k) { return k < 2 ? all() : ((k & 1) ? not_h() : not_a()); }
+    // the post-shift mask of direction k under rule set r: kRulesOthello takes the UNSWAPPED masks (the col-1 rays
+    // -1, -(N+1), +(N-1) clear column N-1, where a wrapped bit lands; the col+1 rays clear column 0), so a ray stops at
+    // the board edge and never wraps -- standard Othello
+    static constexpr uint64_t mask(int k, int r) { return r == 0 ? mask(k) : (k < 2 ? all() : ((k & 1) ? not_a() : not_h())); }
 };
+// Rule sets (OTH_RULES_* of the C ABI).  A compile-time parameter R of every function below, defaulted to the reference's
+// rules: a call site that does not name it compiles to what it compiled to before the selector existed.
+constexpr int kRulesReference = 0;  // the reference's game, swapped masks included: the default, parity-pinned
+constexpr int kRulesOthello = 1;    // standard Othello: same start position, pass action, move / terminal / winner logic
+constexpr bool rules_ok(int r) { return r == kRulesReference || r == kRulesOthello; }
 static_assert(Geo<8>::not_a() == 0xFEFEFEFEFEFEFEFEULL && Geo<8>::not_h() == 0x7F7F7F7F7F7F7F7FULL, "pyx:29,31");
 static_assert(Geo<8>::start_self() == ((1ULL << 28) | (1ULL << 35)) && Geo<8>::start_opp() == ((1ULL << 27) | (1ULL << 36)),
               "pyx:64-65");
+static_assert(Geo<8>::mask(2, 1) == 0x7F7F7F7F7F7F7F7FULL && Geo<8>::mask(3, 1) == 0xFEFEFEFEFEFEFEFEULL &&
+                  Geo<8>::mask(2, 0) == Geo<8>::mask(2) && Geo<8>::mask(0, 1) == ~0ULL, "rule-set masks");
 static_assert(Geo<6>::all() == 0xFFFFFFFFFULL && Geo<6>::not_a() == 0xFBEFBEFBEULL && Geo<6>::not_h() == 0x7DF7DF7DFULL, "6x6 masks");
 
 constexpr uint64_t kNotA = Geo<8>::not_a();
@@ -65,10 +78,10 @@ constexpr uint64_t kStartSelf = Geo<8>::start_self();  // black E4,D5 (pyx:65)
 constexpr uint64_t kStartOpp = Geo<8>::start_opp();    // white D4,E5 (pyx:64)
 
 // one step of a ray in direction K with the reference's post-shift mask (pyx:33-38)
-template <int N, int K>
+template <int N, int K, int R = kRulesReference>
 OTH_HD uint64_t step(uint64_t x) {
     constexpr int d = Geo<N>::delta(K);
-    constexpr uint64_t m = Geo<N>::mask(K);
+    constexpr uint64_t m = Geo<N>::mask(K, R);
     if constexpr (d > 0) return (x << d) & m;
     else return (x >> (-d)) & m;
 }
@@ -83,13 +96,13 @@ OTH_HD uint64_t back(uint64_t x, int n) {
 // Set-wise legal-move generation: all candidate origins advance together, N-2 steps per direction (a ray can hold
 // at most N-2 opponent stones before it must land on an own stone; for N = 8 verified against the compiled
 // reference on 200 799 positions, for N = 6 against the 6x6 oracle).
-template <int N, int K>
+template <int N, int K, int R = kRulesReference>
 OTH_HD uint64_t legal_dir(uint64_t self_b, uint64_t opp_b, uint64_t empty) {
     uint64_t legal = 0;
-    uint64_t x = step<N, K>(empty) & opp_b;  // rays whose first cell is an opponent stone
+    uint64_t x = step<N, K, R>(empty) & opp_b;  // rays whose first cell is an opponent stone
 #pragma unroll
     for (int k = 1; k <= N - 2; ++k) {
-        uint64_t nxt = step<N, K>(x);
+        uint64_t nxt = step<N, K, R>(x);
         legal |= back<N, K>(nxt & self_b, k + 1);  // bracketed: origin is k+1 steps back
         x = nxt & opp_b;
     }
@@ -97,37 +110,37 @@ OTH_HD uint64_t legal_dir(uint64_t self_b, uint64_t opp_b, uint64_t empty) {
 }
 
 // bitboard.pyx:135-158 _compute_legal_moves / :187 get_legal_moves_bits
-template <int N>
+template <int N, int R = kRulesReference>
 OTH_HD uint64_t legal_moves_n(uint64_t self_b, uint64_t opp_b) {
     const uint64_t empty = ~(self_b | opp_b) & Geo<N>::all();
-    uint64_t l = legal_dir<N, 0>(self_b, opp_b, empty) | legal_dir<N, 1>(self_b, opp_b, empty) |
-                 legal_dir<N, 2>(self_b, opp_b, empty) | legal_dir<N, 3>(self_b, opp_b, empty) |
-                 legal_dir<N, 4>(self_b, opp_b, empty) | legal_dir<N, 5>(self_b, opp_b, empty) |
-                 legal_dir<N, 6>(self_b, opp_b, empty) | legal_dir<N, 7>(self_b, opp_b, empty);
+    uint64_t l = legal_dir<N, 0, R>(self_b, opp_b, empty) | legal_dir<N, 1, R>(self_b, opp_b, empty) |
+                 legal_dir<N, 2, R>(self_b, opp_b, empty) | legal_dir<N, 3, R>(self_b, opp_b, empty) |
+                 legal_dir<N, 4, R>(self_b, opp_b, empty) | legal_dir<N, 5, R>(self_b, opp_b, empty) |
+                 legal_dir<N, 6, R>(self_b, opp_b, empty) | legal_dir<N, 7, R>(self_b, opp_b, empty);
     return l & empty;
 }
 OTH_HD uint64_t legal_moves(uint64_t self_b, uint64_t opp_b) { return legal_moves_n<8>(self_b, opp_b); }
 
-template <int N, int K>
+template <int N, int K, int R = kRulesReference>
 OTH_HD uint64_t flip_dir(uint64_t pos_bit, uint64_t self_b, uint64_t opp_b) {  // pyx:71-114
     uint64_t flip = 0;
-    uint64_t cur = step<N, K>(pos_bit);
+    uint64_t cur = step<N, K, R>(pos_bit);
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {  // at most N-1 cells fit on any ray
         const uint64_t on_opp = cur & opp_b;
         flip |= on_opp;
-        cur = on_opp ? step<N, K>(cur) : cur;
+        cur = on_opp ? step<N, K, R>(cur) : cur;
     }
     return (cur & self_b) ? flip : 0;
 }
 
 // bitboard.pyx:116-133 _get_flip_bits (pos in 0..N*N-1)
-template <int N>
+template <int N, int R = kRulesReference>
 OTH_HD uint64_t flip_bits_n(int pos, uint64_t self_b, uint64_t opp_b) {
     const uint64_t p = 1ULL << pos;
-    return flip_dir<N, 0>(p, self_b, opp_b) | flip_dir<N, 1>(p, self_b, opp_b) | flip_dir<N, 2>(p, self_b, opp_b) |
-           flip_dir<N, 3>(p, self_b, opp_b) | flip_dir<N, 4>(p, self_b, opp_b) | flip_dir<N, 5>(p, self_b, opp_b) |
-           flip_dir<N, 6>(p, self_b, opp_b) | flip_dir<N, 7>(p, self_b, opp_b);
+    return flip_dir<N, 0, R>(p, self_b, opp_b) | flip_dir<N, 1, R>(p, self_b, opp_b) | flip_dir<N, 2, R>(p, self_b, opp_b) |
+           flip_dir<N, 3, R>(p, self_b, opp_b) | flip_dir<N, 4, R>(p, self_b, opp_b) | flip_dir<N, 5, R>(p, self_b, opp_b) |
+           flip_dir<N, 6, R>(p, self_b, opp_b) | flip_dir<N, 7, R>(p, self_b, opp_b);
 }
 OTH_HD uint64_t flip_bits(int pos, uint64_t self_b, uint64_t opp_b) { return flip_bits_n<8>(pos, self_b, opp_b); }
 
@@ -155,10 +168,10 @@ OTH_HD void reset_n(Board& b) {  // pyx:52-69
 OTH_HD void reset(Board& b) { reset_n<8>(b); }
 
 // bitboard.pyx:195-247 make_move.  Returns 1 on success; on failure the state is untouched.
-template <int N>
+template <int N, int R = kRulesReference>
 OTH_HD int make_move_n(Board& b, int pos) {
     if (pos == Geo<N>::CELLS) {  // pass is valid only when there is no legal move (pyx:209-219)
-        if (legal_moves_n<N>(b.self_b, b.opp_b) != 0) return 0;
+        if (legal_moves_n<N, R>(b.self_b, b.opp_b) != 0) return 0;
         const uint64_t t = b.self_b;
         b.self_b = b.opp_b;
         b.opp_b = t;
@@ -169,7 +182,7 @@ OTH_HD int make_move_n(Board& b, int pos) {
     if (pos < 0 || pos > Geo<N>::CELLS - 1) return 0;
     const uint64_t bit = 1ULL << pos;
     if ((b.self_b | b.opp_b) & bit) return 0;
-    const uint64_t flip = flip_bits_n<N>(pos, b.self_b, b.opp_b);
+    const uint64_t flip = flip_bits_n<N, R>(pos, b.self_b, b.opp_b);
     if (flip == 0) return 0;
     const uint64_t ns = b.opp_b & ~flip;  // swap sides (pyx:160-164)
     b.opp_b = b.self_b | bit | flip;
@@ -181,12 +194,12 @@ OTH_HD int make_move_n(Board& b, int pos) {
 OTH_HD int make_move(Board& b, int pos) { return make_move_n<8>(b, pos); }
 
 // move already known to be legal (search inner loop): no checks, pass when pos == N*N
-template <int N>
+template <int N, int R = kRulesReference>
 OTH_HD void apply_known_n(uint64_t& self_b, uint64_t& opp_b, int pos) {
     uint64_t flip = 0, bit = 0;
     if (pos < Geo<N>::CELLS) {
         bit = 1ULL << pos;
-        flip = flip_bits_n<N>(pos, self_b, opp_b);
+        flip = flip_bits_n<N, R>(pos, self_b, opp_b);
     }
     const uint64_t ns = opp_b & ~flip;
     opp_b = self_b | bit | flip;
@@ -194,10 +207,10 @@ OTH_HD void apply_known_n(uint64_t& self_b, uint64_t& opp_b, int pos) {
 }
 OTH_HD void apply_known(uint64_t& self_b, uint64_t& opp_b, int pos) { apply_known_n<8>(self_b, opp_b, pos); }
 
-template <int N>
+template <int N, int R = kRulesReference>
 OTH_HD int is_terminal_n(uint64_t self_b, uint64_t opp_b) {  // pyx:249-264
-    if (legal_moves_n<N>(self_b, opp_b) != 0) return 0;
-    return legal_moves_n<N>(opp_b, self_b) == 0;
+    if (legal_moves_n<N, R>(self_b, opp_b) != 0) return 0;
+    return legal_moves_n<N, R>(opp_b, self_b) == 0;
 }
 OTH_HD int is_terminal(uint64_t self_b, uint64_t opp_b) { return is_terminal_n<8>(self_b, opp_b); }
 

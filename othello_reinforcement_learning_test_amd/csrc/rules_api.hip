@@ -67,22 +67,22 @@ int bind_pointer_device(const void* p) {
 }
 
 // -------------------------------------------------------------------------------- kernels
-template <int N>
+template <int N, int R>
 __global__ void k_legal(const uint64_t* __restrict__ s, const uint64_t* __restrict__ o,
                         uint64_t* __restrict__ out, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = legal_moves_n<N>(s[i], o[i]);
+        out[i] = legal_moves_n<N, R>(s[i], o[i]);
 }
 
-template <int N>
+template <int N, int R>
 __global__ void k_make_move(uint64_t* __restrict__ s, uint64_t* __restrict__ o, const int32_t* __restrict__ pos,
                             int32_t* __restrict__ ok, uint64_t* __restrict__ flips, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         Board b{s[i], o[i], 0, 0};
         const int p = pos[i];
         uint64_t f = 0;
-        if (p >= 0 && p < Geo<N>::CELLS && !((b.self_b | b.opp_b) >> p & 1ULL)) f = flip_bits_n<N>(p, b.self_b, b.opp_b);
-        const int r = make_move_n<N>(b, p);
+        if (p >= 0 && p < Geo<N>::CELLS && !((b.self_b | b.opp_b) >> p & 1ULL)) f = flip_bits_n<N, R>(p, b.self_b, b.opp_b);
+        const int r = make_move_n<N, R>(b, p);
         s[i] = b.self_b;
         o[i] = b.opp_b;
         ok[i] = r;
@@ -90,17 +90,17 @@ __global__ void k_make_move(uint64_t* __restrict__ s, uint64_t* __restrict__ o, 
     }
 }
 
-template <int N>
+template <int N, int R>
 __global__ void k_status(const uint64_t* __restrict__ s, const uint64_t* __restrict__ o, int32_t* __restrict__ term,
                          int32_t* __restrict__ win, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        term[i] = is_terminal_n<N>(s[i], o[i]);
+        term[i] = is_terminal_n<N, R>(s[i], o[i]);
         win[i] = winner(s[i], o[i]);
     }
 }
 
 // one wave per position: lane = square, three coalesced row stores per position (256 B on 8x8)
-template <int N>
+template <int N, int R>
 __global__ void k_tensor(const uint64_t* __restrict__ s, const uint64_t* __restrict__ o, float* __restrict__ out,
                          int64_t n) {
     constexpr int CELLS = Geo<N>::CELLS;
@@ -109,7 +109,7 @@ __global__ void k_tensor(const uint64_t* __restrict__ s, const uint64_t* __restr
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t i = wave; i < n; i += nwaves) {
         const uint64_t sb = s[i], ob = o[i];
-        const uint64_t lg = legal_moves_n<N>(sb, ob);
+        const uint64_t lg = legal_moves_n<N, R>(sb, ob);
         float* t = out + i * 3 * CELLS;
         if (lane < CELLS) {
             t[lane] = (sb >> lane) & 1ULL ? 1.0f : 0.0f;
@@ -144,7 +144,7 @@ __host__ __device__ inline uint64_t lcg_skip(uint64_t x, uint64_t k) {
     return am * x + cm;
 }
 
-template <int N>
+template <int N, int R>
 __global__ void k_checksum(int64_t n, int64_t per_thread, Affine* legal_maps, Affine* flip_maps) {
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t lo = t * per_thread, hi = lo + per_thread < n ? lo + per_thread : n;
@@ -158,11 +158,11 @@ __global__ void k_checksum(int64_t n, int64_t per_thread, Affine* legal_maps, Af
             x = x * 6364136223846793005ULL + 1442695040888963407ULL; d = x;
             const uint64_t occ = (i & 1) ? (a | (c & d)) : (a & c);
             const uint64_t sb = occ & d & Geo<N>::all(), ob = occ & ~d & Geo<N>::all();
-            const uint64_t lb = legal_moves_n<N>(sb, ob);
+            const uint64_t lb = legal_moves_n<N, R>(sb, ob);
             la = compose(la, Affine{0x100000001B3ULL, lb});
             if (lb) {
                 const int mv = __ffsll((unsigned long long)lb) - 1;
-                fa = compose(fa, Affine{0x100000001B3ULL, flip_bits_n<N>(mv, sb, ob)});
+                fa = compose(fa, Affine{0x100000001B3ULL, flip_bits_n<N, R>(mv, sb, ob)});
             }
         }
     }
@@ -240,63 +240,82 @@ void oth_board_get_symmetries(const oth_board* b, const float* pi, float* states
 
 // ---- section 2: batched device rules -----------------------------------------------------------
 #define OTH_BOARD_OK(bs, what) OTH_CHECK((bs) == 8 || (bs) == 6, what ": board_size must be 8 or 6")
-int oth_legal_moves_batch_n(int bs, const uint64_t* s, const uint64_t* o, uint64_t* legal, int64_t n, void* stream) {
+#define OTH_RULES_OK(r, what) \
+    OTH_CHECK(rules_ok(r), what ": rules must be OTH_RULES_REFERENCE (0) or OTH_RULES_OTHELLO (1), got %d", (int)(r))
+// run a statement with N = board size and R = rule set as compile-time constants (both already validated)
+#define OTH_DISPATCH_NR(bs, rules, ...)                                  \
+    do {                                                                 \
+        if ((bs) == 8 && (rules) == kRulesReference) {                   \
+            constexpr int N = 8, R = kRulesReference;                    \
+            __VA_ARGS__;                                                 \
+        } else if ((bs) == 6 && (rules) == kRulesReference) {            \
+            constexpr int N = 6, R = kRulesReference;                    \
+            __VA_ARGS__;                                                 \
+        } else if ((bs) == 8) {                                          \
+            constexpr int N = 8, R = kRulesOthello;                      \
+            __VA_ARGS__;                                                 \
+        } else {                                                         \
+            constexpr int N = 6, R = kRulesOthello;                      \
+            __VA_ARGS__;                                                 \
+        }                                                                \
+    } while (0)
+int oth_legal_moves_batch_r(int bs, int rules, const uint64_t* s, const uint64_t* o, uint64_t* legal, int64_t n, void* stream) {
     OTH_NEED_DEVICE();
     OTH_BOARD_OK(bs, "oth_legal_moves_batch");
+    OTH_RULES_OK(rules, "oth_legal_moves_batch");
     OTH_CHECK(n >= 0 && (n == 0 || (s && o && legal)), "oth_legal_moves_batch: null pointer or negative n");
     if (n == 0) return OTH_OK;
     OTH_BIND_PTR(s);
-    if (bs == 8) hipLaunchKernelGGL(k_legal<8>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, legal, n);
-    else hipLaunchKernelGGL(k_legal<6>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, legal, n);
+    OTH_DISPATCH_NR(bs, rules, hipLaunchKernelGGL((k_legal<N, R>), dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, legal, n));
     OTH_HIP(hipGetLastError());
     return OTH_OK;
 }
-int oth_make_move_batch_n(int bs, uint64_t* s, uint64_t* o, const int32_t* pos, int32_t* ok, uint64_t* flips, int64_t n,
+int oth_make_move_batch_r(int bs, int rules, uint64_t* s, uint64_t* o, const int32_t* pos, int32_t* ok, uint64_t* flips, int64_t n,
                           void* stream) {
     OTH_NEED_DEVICE();
     OTH_BOARD_OK(bs, "oth_make_move_batch");
+    OTH_RULES_OK(rules, "oth_make_move_batch");
     OTH_CHECK(n >= 0 && (n == 0 || (s && o && pos && ok)), "oth_make_move_batch: null pointer or negative n");
     if (n == 0) return OTH_OK;
     OTH_BIND_PTR(s);
-    if (bs == 8) hipLaunchKernelGGL(k_make_move<8>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, pos, ok, flips, n);
-    else hipLaunchKernelGGL(k_make_move<6>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, pos, ok, flips, n);
+    OTH_DISPATCH_NR(bs, rules, hipLaunchKernelGGL((k_make_move<N, R>), dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, pos, ok, flips, n));
     OTH_HIP(hipGetLastError());
     return OTH_OK;
 }
-int oth_status_batch_n(int bs, const uint64_t* s, const uint64_t* o, int32_t* term, int32_t* win, int64_t n, void* stream) {
+int oth_status_batch_r(int bs, int rules, const uint64_t* s, const uint64_t* o, int32_t* term, int32_t* win, int64_t n, void* stream) {
     OTH_NEED_DEVICE();
     OTH_BOARD_OK(bs, "oth_status_batch");
+    OTH_RULES_OK(rules, "oth_status_batch");
     OTH_CHECK(n >= 0 && (n == 0 || (s && o && term && win)), "oth_status_batch: null pointer or negative n");
     if (n == 0) return OTH_OK;
     OTH_BIND_PTR(s);
-    if (bs == 8) hipLaunchKernelGGL(k_status<8>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, term, win, n);
-    else hipLaunchKernelGGL(k_status<6>, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, term, win, n);
+    OTH_DISPATCH_NR(bs, rules, hipLaunchKernelGGL((k_status<N, R>), dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), s, o, term, win, n));
     OTH_HIP(hipGetLastError());
     return OTH_OK;
 }
-int oth_tensor_input_batch_n(int bs, const uint64_t* s, const uint64_t* o, float* out, int64_t n, void* stream) {
+int oth_tensor_input_batch_r(int bs, int rules, const uint64_t* s, const uint64_t* o, float* out, int64_t n, void* stream) {
     OTH_NEED_DEVICE();
     OTH_BOARD_OK(bs, "oth_tensor_input_batch");
+    OTH_RULES_OK(rules, "oth_tensor_input_batch");
     OTH_CHECK(n >= 0 && (n == 0 || (s && o && out)), "oth_tensor_input_batch: null pointer or negative n");
     if (n == 0) return OTH_OK;
     OTH_BIND_PTR(s);
     const dim3 grid(grid_for((n + 3) / 4 * 256, 256));
-    if (bs == 8) hipLaunchKernelGGL(k_tensor<8>, grid, dim3(256), 0, as_stream(stream), s, o, out, n);
-    else hipLaunchKernelGGL(k_tensor<6>, grid, dim3(256), 0, as_stream(stream), s, o, out, n);
+    OTH_DISPATCH_NR(bs, rules, hipLaunchKernelGGL((k_tensor<N, R>), grid, dim3(256), 0, as_stream(stream), s, o, out, n));
     OTH_HIP(hipGetLastError());
     return OTH_OK;
 }
-int oth_rules_checksum_n(int bs, int64_t n, uint64_t* legal_acc, uint64_t* flip_acc, void* stream) {
+int oth_rules_checksum_r(int bs, int rules, int64_t n, uint64_t* legal_acc, uint64_t* flip_acc, void* stream) {
     OTH_NEED_DEVICE();
     OTH_BOARD_OK(bs, "oth_rules_checksum");
+    OTH_RULES_OK(rules, "oth_rules_checksum");
     OTH_CHECK(n >= 0 && legal_acc && flip_acc, "oth_rules_checksum: bad arguments");
     const int threads = 256 * 1024;
     const int64_t per = (n + threads - 1) / threads > 0 ? (n + threads - 1) / threads : 1;
     Affine *dl = nullptr, *df = nullptr;
     OTH_HIP(hipMalloc(&dl, sizeof(Affine) * threads));
     OTH_HIP(hipMalloc(&df, sizeof(Affine) * threads));
-    if (bs == 8) hipLaunchKernelGGL(k_checksum<8>, dim3(threads / 256), dim3(256), 0, as_stream(stream), n, per, dl, df);
-    else hipLaunchKernelGGL(k_checksum<6>, dim3(threads / 256), dim3(256), 0, as_stream(stream), n, per, dl, df);
+    OTH_DISPATCH_NR(bs, rules, hipLaunchKernelGGL((k_checksum<N, R>), dim3(threads / 256), dim3(256), 0, as_stream(stream), n, per, dl, df));
     Affine* hl = new Affine[threads];
     Affine* hf = new Affine[threads];
     hipError_t e1 = hipMemcpyAsync(hl, dl, sizeof(Affine) * threads, hipMemcpyDeviceToHost, as_stream(stream));
@@ -317,6 +336,23 @@ int oth_rules_checksum_n(int bs, int64_t n, uint64_t* legal_acc, uint64_t* flip_
     *legal_acc = la;
     *flip_acc = fa;
     return OTH_OK;
+}
+// the `_n` forms: the reference's rules on either board
+int oth_legal_moves_batch_n(int bs, const uint64_t* s, const uint64_t* o, uint64_t* legal, int64_t n, void* stream) {
+    return oth_legal_moves_batch_r(bs, OTH_RULES_REFERENCE, s, o, legal, n, stream);
+}
+int oth_make_move_batch_n(int bs, uint64_t* s, uint64_t* o, const int32_t* pos, int32_t* ok, uint64_t* flips, int64_t n,
+                          void* stream) {
+    return oth_make_move_batch_r(bs, OTH_RULES_REFERENCE, s, o, pos, ok, flips, n, stream);
+}
+int oth_status_batch_n(int bs, const uint64_t* s, const uint64_t* o, int32_t* term, int32_t* win, int64_t n, void* stream) {
+    return oth_status_batch_r(bs, OTH_RULES_REFERENCE, s, o, term, win, n, stream);
+}
+int oth_tensor_input_batch_n(int bs, const uint64_t* s, const uint64_t* o, float* out, int64_t n, void* stream) {
+    return oth_tensor_input_batch_r(bs, OTH_RULES_REFERENCE, s, o, out, n, stream);
+}
+int oth_rules_checksum_n(int bs, int64_t n, uint64_t* legal_acc, uint64_t* flip_acc, void* stream) {
+    return oth_rules_checksum_r(bs, OTH_RULES_REFERENCE, n, legal_acc, flip_acc, stream);
 }
 // the reference's board (8x8): the original entry points
 int oth_legal_moves_batch(const uint64_t* s, const uint64_t* o, uint64_t* legal, int64_t n, void* stream) {
@@ -355,6 +391,48 @@ int oth_board_make_move_n(int bs, oth_board* b, int pos) {
 }
 int oth_board_is_terminal_n(int bs, const oth_board* b) {
     return bs == 6 ? is_terminal_n<6>(b->self_board, b->opp_board) : is_terminal_n<8>(b->self_board, b->opp_board);
+}
+
+
+// ---- rule-set forms of the host functions: board_size 8 or 6, rules OTH_RULES_REFERENCE or OTH_RULES_OTHELLO.  An unknown
+// board size or rule set is an error with a message (the status-returning forms) or yields 0 with the message set.
+static bool host_args_ok(int bs, int rules, const char* what) {
+    if (bs != 8 && bs != 6) { set_error("%s: board_size must be 8 or 6, got %d", what, bs); return false; }
+    if (!rules_ok(rules)) {
+        set_error("%s: rules must be OTH_RULES_REFERENCE (0) or OTH_RULES_OTHELLO (1), got %d", what, rules);
+        return false;
+    }
+    return true;
+}
+int oth_board_reset_r(int bs, int rules, oth_board* b) {
+    if (!host_args_ok(bs, rules, "oth_board_reset_r")) return OTH_E_INVALID;
+    oth_board_reset_n(bs, b);  // the start position is the same under both rule sets
+    return OTH_OK;
+}
+uint64_t oth_legal_moves_r(int bs, int rules, uint64_t s, uint64_t o) {
+    if (!host_args_ok(bs, rules, "oth_legal_moves_r")) return 0;
+    if (rules == OTH_RULES_REFERENCE) return oth_legal_moves_n(bs, s, o);
+    return bs == 6 ? legal_moves_n<6, kRulesOthello>(s, o) : legal_moves_n<8, kRulesOthello>(s, o);
+}
+uint64_t oth_flip_bits_r(int bs, int rules, int pos, uint64_t s, uint64_t o) {
+    if (!host_args_ok(bs, rules, "oth_flip_bits_r")) return 0;
+    if (rules == OTH_RULES_REFERENCE) return oth_flip_bits_n(bs, pos, s, o);
+    if (pos < 0 || pos >= bs * bs) return 0;
+    return bs == 6 ? flip_bits_n<6, kRulesOthello>(pos, s, o) : flip_bits_n<8, kRulesOthello>(pos, s, o);
+}
+int oth_board_make_move_r(int bs, int rules, oth_board* b, int pos) {
+    if (!host_args_ok(bs, rules, "oth_board_make_move_r")) return 0;
+    if (rules == OTH_RULES_REFERENCE) return oth_board_make_move_n(bs, b, pos);
+    Board t{b->self_board, b->opp_board, b->move_count, b->passed};
+    const int r = bs == 6 ? make_move_n<6, kRulesOthello>(t, pos) : make_move_n<8, kRulesOthello>(t, pos);
+    b->self_board = t.self_b; b->opp_board = t.opp_b; b->move_count = t.move_count; b->passed = t.passed;
+    return r;
+}
+int oth_board_is_terminal_r(int bs, int rules, const oth_board* b) {
+    if (!host_args_ok(bs, rules, "oth_board_is_terminal_r")) return 0;
+    if (rules == OTH_RULES_REFERENCE) return oth_board_is_terminal_n(bs, b);
+    return bs == 6 ? is_terminal_n<6, kRulesOthello>(b->self_board, b->opp_board)
+                   : is_terminal_n<8, kRulesOthello>(b->self_board, b->opp_board);
 }
 
 }  // extern "C"

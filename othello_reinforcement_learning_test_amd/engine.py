@@ -434,7 +434,7 @@ class LaneOverlapCheck:
                 "arrangements_tried": [h[1]["overlap"] for h in self.history]}
 
 
-def policy_from_visits(visits, self_b, opp_b, temperature, board_size=8):
+def policy_from_visits(visits, self_b, opp_b, temperature, board_size=8, rules="reference"):
     """MCTSNode.get_policy_distribution for a general temperature (/root/reference/src/mcts/node.py:162-182), the same
     numpy expressions in the same order on the root's children (= the legal moves in ascending order, or the pass):
     float32 counts ** (1.0 / T), /= counts.sum(), scatter.  Bit-identical to the reference by construction.
@@ -447,7 +447,7 @@ def policy_from_visits(visits, self_b, opp_b, temperature, board_size=8):
     (a deliberate deviation; parity unpinned: no fixture has zero simulations)."""
     npol = board_size * board_size + 1
     policy = np.zeros(npol, dtype=np.float32)
-    legal = int(_lib.load().oth_legal_moves_n(board_size, self_b, opp_b))
+    legal = int(_lib.load().oth_legal_moves_r(board_size, _lib.rules_id(rules), self_b, opp_b))
     actions = [a for a in range(npol - 1) if (legal >> a) & 1] or [npol - 1]
     counts = np.array([visits[a] for a in actions], dtype=np.float32)
     if temperature != 0 and not counts.any():
@@ -467,8 +467,9 @@ class SearchEngine:
 
     def __init__(self, max_games, num_simulations, temperature_threshold=15, c_puct=1.0,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, store_late_onehot=False, evaluator=None,
-                 eval_cache_log2=0, board_size=None):
+                 eval_cache_log2=0, board_size=None, rules="reference"):
         _lib.require_device()
+        self.rules = _lib.rules_name(rules)   # "reference" (the default: the reference's game) or "othello" (standard)
         self.max_games = int(max_games)
         self.num_simulations = int(num_simulations)
         if board_size is None:   # follow the evaluator's network; 8 (the reference's game) otherwise
@@ -478,7 +479,8 @@ class SearchEngine:
         self.npol = self.cells + 1
         cfg = _lib.EngineCfg(self.max_games, self.num_simulations, int(temperature_threshold),
                              float(c_puct), float(dirichlet_alpha), float(dirichlet_epsilon),
-                             1 if store_late_onehot else 0, int(eval_cache_log2), self.board_size)
+                             1 if store_late_onehot else 0, int(eval_cache_log2), self.board_size,
+                             _lib.rules_id(rules))
         self._h = _lib.load().oth_engine_create(C.byref(cfg))
         if not self._h:
             raise _lib.OthelloHipError("oth_engine_create: " + _lib.last_error())
@@ -527,7 +529,7 @@ class SearchEngine:
         if temperature not in (0, 0.0, 1, 1.0):
             _, visits, wsum, prior = self.search_results(1.0)
             pi = np.stack([policy_from_visits(visits[i], int(self._roots[0][i]), int(self._roots[1][i]), temperature,
-                                              self.board_size) for i in range(self._n)])
+                                              self.board_size, self.rules) for i in range(self._n)])
             return pi, visits, wsum, prior
         n = self._n
         pi = np.zeros((n, self.npol), dtype=np.float32)

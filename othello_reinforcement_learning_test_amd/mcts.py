@@ -11,6 +11,7 @@ reference does (mcts.py:221), so a seeded run consumes the same random stream.
 """
 import numpy as np
 
+from . import _lib
 from .engine import HipResNetEvaluator, SearchEngine
 
 
@@ -44,19 +45,19 @@ class MCTS:
         self.evaluator = HipResNetEvaluator(model, precision=precision, calibrate=True)
         self._engines = {}
 
-    def _engine(self, num_simulations, max_games=1):
-        key = (int(num_simulations), int(max_games))
+    def _engine(self, num_simulations, max_games=1, rules="reference"):
+        key = (int(num_simulations), int(max_games), rules)
         eng = self._engines.get(key)
         if eng is None:
             eng = SearchEngine(max_games, num_simulations, c_puct=self.c_puct,
                                dirichlet_alpha=self.dirichlet_alpha,
-                               dirichlet_epsilon=self.dirichlet_epsilon, evaluator=self.evaluator)
+                               dirichlet_epsilon=self.dirichlet_epsilon, evaluator=self.evaluator, rules=rules)
             self._engines[key] = eng
         return eng
 
     def _search_stats(self, board, num_simulations, temperature):
         self.evaluator.refresh()
-        eng = self._engine(num_simulations)
+        eng = self._engine(num_simulations, rules=_lib.common_rules([board]))   # the board's own rule set
         eng.search_begin([board.self_board], [board.opp_board])
         eng.search_run_rescued()   # (a launch that clamped an activation is run again at a lower activation scale)
         return eng.search_results(temperature)

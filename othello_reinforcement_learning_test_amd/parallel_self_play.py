@@ -13,6 +13,7 @@ import time
 
 import numpy as np
 
+from . import _lib
 from .engine import HipResNetEvaluator, LaneOverlapCheck, SearchEngine, lane_streams
 from .self_play import tuples_from_arrays
 
@@ -35,17 +36,17 @@ class BatchMCTS:
         self._external = hasattr(self.evaluator, "host_eval")
         self._engines = {}
 
-    def _engine(self, n_boards, num_simulations):
+    def _engine(self, n_boards, num_simulations, rules="reference"):
         cap = 1
         while cap < n_boards:
             cap *= 2
-        key = (cap, int(num_simulations))
+        key = (cap, int(num_simulations), rules)
         eng = self._engines.get(key)
         if eng is None:
             eng = SearchEngine(cap, num_simulations, c_puct=self.c_puct,
                                dirichlet_alpha=self.dirichlet_alpha,
                                dirichlet_epsilon=self.dirichlet_epsilon,
-                               evaluator=None if self._external else self.evaluator)
+                               evaluator=None if self._external else self.evaluator, rules=rules)
             self._engines[key] = eng
         return eng
 
@@ -53,12 +54,13 @@ class BatchMCTS:
         n = len(boards)
         if n == 0:
             return []
+        rules = _lib.common_rules(boards)   # one rule set per call: a mix is a ValueError
         if not self._external:
             self.evaluator.refresh()
         if add_dirichlet_noise:  # :111-118: one draw per board, in board order
             for b in boards:
                 np.random.dirichlet([self.dirichlet_alpha] * len(b.get_legal_moves()))
-        eng = self._engine(n, num_simulations)
+        eng = self._engine(n, num_simulations, rules)
         sb, ob = [b.self_board for b in boards], [b.opp_board for b in boards]
         if self._external:
             pi, _, _, _ = eng.search_with(sb, ob, self.evaluator.host_eval, float(temperature))
@@ -75,6 +77,9 @@ class ParallelSelfPlayWorker:
                  rng_mode=None, precision=None, verbose=True, eval_cache_log2=0, lanes=None, continuous=False,
                  stagger_rounds=0, device_slots=None):
         self.board_class = board_class
+        # the rule set every engine of this worker plays (lane engines and a grown engine included) and the class of the
+        # numpy-RNG mode's host mirror boards: the board class's
+        self.rules = _lib.rules_name(getattr(board_class, "rules", "reference"))
         self.num_simulations = num_simulations
         self.temperature_threshold = temperature_threshold
         self.num_parallel_games = num_parallel_games
@@ -93,12 +98,12 @@ class ParallelSelfPlayWorker:
         self.device_slots = None if device_slots is None else int(device_slots)
         self._engine_args = dict(temperature_threshold=temperature_threshold, c_puct=c_puct,
                                  dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                                 store_late_onehot=False, eval_cache_log2=eval_cache_log2)
+                                 store_late_onehot=False, eval_cache_log2=eval_cache_log2, rules=self.rules)
         self.engine = SearchEngine(self.device_slots or num_parallel_games, num_simulations,
                                    temperature_threshold=temperature_threshold, c_puct=c_puct,
                                    dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                                    store_late_onehot=False, evaluator=self.batch_mcts.evaluator,
-                                   eval_cache_log2=eval_cache_log2)
+                                   eval_cache_log2=eval_cache_log2, rules=self.rules)
         # lanes > 1 (device RNG mode): the slots are split into independent groups, each an engine on its own
         # stream and host thread; their kernels overlap on the device (one group's network launches fill the
         # other's tails and tree-search phases: +4 % at 4096 slots).  Results are concatenated lane by lane.
@@ -111,7 +116,8 @@ class ParallelSelfPlayWorker:
             self._lane_engines = [SearchEngine(per, num_simulations, temperature_threshold=temperature_threshold,
                                                c_puct=c_puct, dirichlet_alpha=dirichlet_alpha,
                                                dirichlet_epsilon=dirichlet_epsilon, store_late_onehot=False,
-                                               evaluator=self.batch_mcts.evaluator, eval_cache_log2=eval_cache_log2)
+                                               evaluator=self.batch_mcts.evaluator, eval_cache_log2=eval_cache_log2,
+                                               rules=self.rules)
                                   for _ in range(self.lanes)]
         # continuous=True (device RNG only): the slots keep playing BETWEEN execute_episodes calls (oth_stream_*): a call
         # returns the games that finished during it -- at least num_episodes -- and leaves the others in flight, so
@@ -311,7 +317,10 @@ class ParallelSelfPlayWorker:
 def create_parallel_self_play_worker(config, model, device=None, **kwargs):
     """Build from a reference YAML config dict (parallel_self_play.py:410-434); same keys, same
     defaults."""
-    from .bitboard import OthelloBitboard
+    from .bitboard import OthelloBitboard, StandardOthelloBitboard
+    # `game.rules` -- a key of THIS package (absent = "reference" = the reference's game): "othello" plays standard Othello
+    rules = _lib.rules_name((config.get("game") or {}).get("rules", "reference"))
+    board_class = StandardOthelloBitboard if rules == "othello" else OthelloBitboard
     mcts = config.get("mcts", {})
     sp = config.get("self_play", {})
     # `self_play.continuous: true` -- a key of THIS package, absent from the reference's YAML files (absent = off = the
@@ -329,7 +338,7 @@ def create_parallel_self_play_worker(config, model, device=None, **kwargs):
     if "device_slots" in sp:
         kwargs.setdefault("device_slots", int(sp["device_slots"]))
     return ParallelSelfPlayWorker(
-        board_class=OthelloBitboard,
+        board_class=board_class,
         model=model,
         device=device,
         num_simulations=mcts.get("num_simulations", 25),

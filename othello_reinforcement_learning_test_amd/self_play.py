@@ -19,6 +19,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _lib
 from .engine import SearchEngine
 
 MAX_CONCURRENT_GAMES = 4096
@@ -48,6 +49,7 @@ def tuples_from_arrays(states, pis, zs, block=512):
 class SelfPlayWorker:
     def __init__(self, board_class, mcts, num_simulations=25, temperature_threshold=15, rng_mode=None):
         self.board_class = board_class
+        self.rules = _lib.rules_name(getattr(board_class, "rules", "reference"))   # the device engine plays the class's rules
         self.mcts = mcts
         self.num_simulations = num_simulations
         self.temperature_threshold = temperature_threshold
@@ -87,7 +89,7 @@ class SelfPlayWorker:
                 g, self.num_simulations, temperature_threshold=self.temperature_threshold,
                 c_puct=self.mcts.c_puct, dirichlet_alpha=self.mcts.dirichlet_alpha,
                 dirichlet_epsilon=self.mcts.dirichlet_epsilon, store_late_onehot=True,
-                evaluator=self.mcts.evaluator)
+                evaluator=self.mcts.evaluator, rules=self.rules)
         return self._engine
 
     def execute_episodes(self, num_episodes, add_dirichlet_noise=True):

@@ -1,0 +1,462 @@
+"""The rule-set selector on the device: the batched rules kernels, the tree search and self-play under
+OTH_RULES_OTHELLO (standard Othello) against the published perft series, the row/column ray walk and the Python search
+of tests/std_rules_ref.py (trusted because it reproduces the C oracle under the reference's masks:
+tests/test_std_rules_cpu.py); and the same entry points at rules 0 against what they gave before the selector existed."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib as ol
+import std_rules_ref as sr
+from stub_eval import stub_probs_values
+
+pytestmark = pytest.mark.gpu
+U64 = np.uint64
+REF, STD = 0, 1
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import othello_reinforcement_learning_test_amd as p
+    p._lib.require_device()
+    return p
+
+
+def dev_u64(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
+
+
+def host_u64(t):
+    return t.cpu().numpy().view(U64)
+
+
+def bits_of(planes):
+    """[n, cells] 0/1 -> uint64[n]"""
+    w = U64(1) << np.arange(planes.shape[1], dtype=U64)
+    return (planes.astype(U64) * w[None, :]).sum(axis=1, dtype=U64)
+
+
+def unpack(bits, cells):
+    return ((np.asarray(bits, dtype=U64)[:, None] >> np.arange(cells, dtype=U64)[None, :]) & U64(1)).astype(np.uint8)
+
+
+# ---- 1. device perft -----------------------------------------------------------------------------------------------
+def device_frontiers(pkg, bs, depth, rules):
+    """Breadth-first expansion on the device: -> [(self u64[], opp u64[], dead)] for depths 1..depth (move sequences, not
+    merged; dead = sequences that ended at a position where neither side can move)."""
+    DB = pkg.DeviceBoards
+    cells = bs * bs
+    s0, o0 = sr.start_position(bs)
+    s, o = dev_u64([s0]), dev_u64([o0])
+    sq = torch.arange(cells, device="cuda", dtype=torch.int64)
+    dead, out = 0, []
+    for _ in range(depth):
+        lg = DB.legal_moves(s, o, bs, rules=rules)
+        term, _ = DB.status(s, o, bs, rules=rules)
+        assert bool(((lg != 0) & (term != 0)).sum() == 0), "a terminal position with a legal move"
+        dead += int((term != 0).sum())
+        has = ((lg[:, None] >> sq[None, :]) & 1) != 0                    # [n, cells]
+        parent, pos = has.nonzero(as_tuple=True)
+        passing = ((lg == 0) & (term == 0)).nonzero(as_tuple=True)[0]     # no move, but the other side has one: pass
+        parent = torch.cat([parent, passing])
+        pos = torch.cat([pos, torch.full_like(passing, cells)]).to(torch.int32).contiguous()
+        s, o = s[parent].contiguous(), o[parent].contiguous()
+        ok, _ = DB.make_move(s, o, pos, bs, rules=rules)
+        assert bool((ok == 1).all()), "make_move refused a move of the legal mask"
+        out.append((host_u64(s), host_u64(o), dead))
+    return out
+
+
+@pytest.mark.parametrize("bs,depth", [(8, 8), (6, 7)])
+def test_device_perft_othello(pkg, bs, depth):
+    fr = device_frontiers(pkg, bs, depth, "othello")
+    counts = [len(s) + dead for s, _, dead in fr]
+    print("device perft %dx%d:" % (bs, bs), counts)
+    assert counts == sr.PERFT[("othello", bs)][:depth]
+    # the depth-5 frontier, element for element, against the host ABI's
+    hf, _ = sr.host_frontiers(bs, STD, 5)[4]
+    want = np.array(sorted(k for k, m in hf.items() for _ in range(m)), dtype=U64)
+    s5, o5, _ = fr[4]
+    order = np.lexsort((o5, s5))
+    assert np.array_equal(np.stack([s5[order], o5[order]], axis=1), want)
+
+
+@pytest.mark.parametrize("bs", [8, 6])
+def test_device_perft_reference_rules_differ(pkg, bs):
+    """The same expansion at rules="reference" gives the reference game's count at the first discriminating depth."""
+    depth, want = sr.PERFT_REFERENCE[bs]
+    fr = device_frontiers(pkg, bs, depth, "reference")
+    assert len(fr[-1][0]) + fr[-1][2] == want
+    # ... and the default argument is that rule set
+    s, o, _ = fr[2]
+    a = pkg.DeviceBoards.legal_moves(dev_u64(s), dev_u64(o), bs)
+    b = pkg.DeviceBoards.legal_moves(dev_u64(s), dev_u64(o), bs, rules="reference")
+    assert torch.equal(a, b)
+
+
+def test_device_rules_refuse_an_unknown_rule_set(pkg):
+    s, o = dev_u64([1]), dev_u64([2])
+    out = torch.empty_like(s)
+    rc = pkg._lib.load().oth_legal_moves_batch_r(8, 7, s.data_ptr(), o.data_ptr(), out.data_ptr(), 1, None)
+    assert rc == -2 and "rules" in pkg._lib.last_error()
+    with pytest.raises(ValueError):
+        pkg.DeviceBoards.legal_moves(s, o, 8, rules="draughts")
+    with pytest.raises(ValueError):
+        pkg.SearchEngine(4, 4, rules="draughts")
+    cfg = pkg._lib.EngineCfg(4, 4, 15, 1.0, 0.3, 0.25, 0, 0, 8, 2)
+    assert not pkg._lib.load().oth_engine_create(C.byref(cfg)) and "rules" in pkg._lib.last_error()
+
+
+# ---- 2. checksum kernel against a host-side fold -----------------------------------------------------------------------
+def host_checksum(pkg, bs, rules, n):
+    """The fold of k_checksum restated over oth_legal_moves_r / oth_flip_bits_r: the same LCG position stream."""
+    L = pkg._lib.load()
+    M64 = (1 << 64) - 1
+    A, Cc, MUL = 6364136223846793005, 1442695040888963407, 0x100000001B3
+    full = (1 << (bs * bs)) - 1
+    x, la, fa = 0x9E3779B97F4A7C15, 0, 0
+    for i in range(n):
+        a = x = (x * A + Cc) & M64
+        c = x = (x * A + Cc) & M64
+        d = x = (x * A + Cc) & M64
+        occ = (a | (c & d)) if i & 1 else (a & c)
+        sb, ob = occ & d & full, occ & ~d & full
+        lb = L.oth_legal_moves_r(bs, rules, sb, ob)
+        la = (la * MUL + lb) & M64
+        if lb:
+            mv = (lb & -lb).bit_length() - 1
+            fa = (fa * MUL + L.oth_flip_bits_r(bs, rules, mv, sb, ob)) & M64
+    return la, fa
+
+
+def device_checksum(pkg, name, *args):
+    la, fa = C.c_uint64(0), C.c_uint64(0)
+    pkg._lib.call(name, *args, C.byref(la), C.byref(fa), None)
+    return la.value, fa.value
+
+
+@pytest.mark.parametrize("bs,n", [(8, 20000), (6, 20000), (8, 300001)])
+def test_rules_checksum_r_equals_the_host_fold(pkg, bs, n):
+    """n = 300 001 > the kernel's 262 144 threads: every thread folds a chunk of two positions."""
+    got = device_checksum(pkg, "oth_rules_checksum_r", bs, STD, n)
+    assert got == host_checksum(pkg, bs, STD, n)
+    ref = device_checksum(pkg, "oth_rules_checksum_r", bs, REF, n)
+    assert ref == device_checksum(pkg, "oth_rules_checksum_n", bs, n) and ref != got
+    if n == 20000:
+        assert ref == host_checksum(pkg, bs, REF, n)
+
+
+# ---- 3. symmetry ---------------------------------------------------------------------------------------------------
+def sym_perm(bs, k):
+    """perm[dst] = src of variant k of get_symmetries (rot90^(k>>1) counter-clockwise, then left-right flip for odd k)."""
+    perm = np.zeros(bs * bs, dtype=np.int64)
+    for r in range(bs):
+        for c in range(bs):
+            cc = bs - 1 - c if k & 1 else c
+            sr_, sc = [(r, cc), (cc, bs - 1 - r), (bs - 1 - r, bs - 1 - cc), (bs - 1 - cc, r)][k >> 1]
+            perm[r * bs + c] = sr_ * bs + sc
+    return perm
+
+
+@pytest.mark.parametrize("bs", [8, 6])
+def test_legal_moves_commute_with_the_board_symmetries(pkg, bs):
+    """Standard Othello is invariant under the 8 symmetries of the square; the reference's game is not (its rays wrap
+    in one direction only), which shows the check can fail."""
+    cells = bs * bs
+    pos = [(s, o) for g in sr.random_games(bs, STD, 200, 20250 + bs) for (s, o, _) in g][:4096]
+    assert len(pos) == 4096
+    s = np.array([p[0] for p in pos], dtype=U64)
+    o = np.array([p[1] for p in pos], dtype=U64)
+    ps, po = unpack(s, cells), unpack(o, cells)
+    DB = pkg.DeviceBoards
+    for rules, must_hold in (("othello", True), ("reference", False)):
+        base = unpack(host_u64(DB.legal_moves(dev_u64(s), dev_u64(o), bs, rules=rules)), cells)
+        violations = 0
+        for k in range(8):
+            perm = sym_perm(bs, k)
+            ts, to = bits_of(ps[:, perm]), bits_of(po[:, perm])
+            got = host_u64(DB.legal_moves(dev_u64(ts), dev_u64(to), bs, rules=rules))
+            violations += int((got != bits_of(base[:, perm])).sum())
+        print("%dx%d %s: %d of %d transformed positions violate the symmetry" % (bs, bs, rules, violations, 8 * 4096))
+        assert (violations == 0) if must_hold else (violations >= 1)
+
+
+def test_sym_perm_is_the_library_transform(pkg):
+    b = pkg.OthelloBitboard()
+    pi = np.arange(65, dtype=np.float32)
+    for k, (_, p) in enumerate(b.get_symmetries(pi)):
+        assert np.array_equal(p[:64], pi[:64][sym_perm(8, k)])
+
+
+# ---- 4. search -----------------------------------------------------------------------------------------------------
+_WANT = {}
+
+
+def want_search(bs, sims, cp):
+    """py_search of the 64 roots of a board size under standard rules (computed once per (board, sims, c_puct))."""
+    key = (bs, sims, cp)
+    if key not in _WANT:
+        rules = _WANT.setdefault(("rules", bs), sr.RayRules(bs))
+        fn = sr.stub_eval_fn(bs * bs + 1)
+        roots = sr.search_roots(bs, STD, 64)
+        _WANT[key] = (roots, [sr.py_search(rules, s, o, sims, cp, fn) for s, o in roots])
+    return _WANT[key]
+
+
+def stub_host_eval(npol):
+    table = sr.stub_table()
+    return lambda s, o, lg: stub_probs_values(s, o, table, npol)
+
+
+@pytest.mark.parametrize("cp", [1.0, 1.5])
+@pytest.mark.parametrize("sims", [5, 50])
+@pytest.mark.parametrize("n", [5, 64])
+@pytest.mark.parametrize("bs", [8, 6])
+def test_search_othello_equals_the_python_search(pkg, bs, n, sims, cp):
+    roots, want = want_search(bs, sims, cp)
+    rules = sr.RayRules(bs)
+    assert rules.legal(*roots[0]) == 0 and rules.legal(roots[0][1], roots[0][0]) != 0      # a root that must pass
+    assert rules.legal(*roots[1]) == 0 and rules.legal(roots[1][1], roots[1][0]) == 0      # a terminal root
+    eng = pkg.SearchEngine(n, sims, c_puct=cp, board_size=bs, rules="othello")
+    assert eng.rules == "othello"
+    pi, visits, wsum, prior = eng.search_with([r[0] for r in roots[:n]], [r[1] for r in roots[:n]],
+                                              stub_host_eval(bs * bs + 1))
+    for i in range(n):
+        wv, ww, wp, wpi = want[i]
+        assert np.array_equal(visits[i], wv), "visits of root %d" % i
+        assert np.array_equal(wsum[i], ww), "value sums of root %d" % i
+        assert np.array_equal(prior[i], wp), "priors of root %d" % i
+        assert np.array_equal(pi[i], wpi), "pi of root %d" % i
+    assert int(visits.sum()) == n * sims
+
+
+@pytest.mark.parametrize("bs", [8, 6])
+def test_search_at_rules_reference_still_equals_the_oracle(pkg, bs):
+    """The same call with rules="reference" (and with no rules argument) is the parity-pinned search."""
+    if bs == 6:
+        import oracle_lib6 as olib
+    else:
+        olib = ol
+    npol = bs * bs + 1
+    table = sr.stub_table()
+    ev = olib.make_eval(lambda s, o: stub_probs_values(s, o, table, npol))
+    roots = sr.search_roots(bs, STD, 5)      # (any positions do: a passing and a terminal one under standard rules first)
+    sb, ob = [r[0] for r in roots], [r[1] for r in roots]
+    a = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs, rules="reference").search_with(sb, ob, stub_host_eval(npol))
+    b = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs).search_with(sb, ob, stub_host_eval(npol))
+    c = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs, rules="othello").search_with(sb, ob, stub_host_eval(npol))
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert not np.array_equal(a[1], c[1])
+    for i, (s, o) in enumerate(roots):
+        opi, on, ow, opr = olib.search(olib.board(s, o), 50, 1.5, 1.0, ev)
+        assert np.array_equal(a[1][i], on) and np.array_equal(a[2][i], ow)
+        assert np.array_equal(a[0][i], opi) and np.array_equal(a[3][i], opr.astype(np.float32))
+
+
+# ---- 5. self-play --------------------------------------------------------------------------------------------------
+def check_stream(bs, states, pis, zs, n_games, game_len=None):
+    """Replay every game of a self-play stream with the ray-walk board (see the checks in the issue's list)."""
+    cells = bs * bs
+    s0, o0 = sr.start_position(bs)
+    st = states.reshape(len(states), 3, cells)
+    assert set(np.unique(st)) <= {0.0, 1.0}
+    sb, ob, lb = (bits_of(st[:, j]) for j in range(3))
+    starts = [i for i in range(len(zs)) if (int(sb[i]), int(ob[i])) == (s0, o0)]
+    assert len(starts) == n_games, "games in the stream"
+    bounds = starts + [len(zs)]
+    if game_len is not None:
+        assert [bounds[g + 1] - bounds[g] for g in range(n_games)] == list(game_len)
+    passes = 0
+    for g in range(n_games):
+        lo, hi = bounds[g], bounds[g + 1]
+        winners = set()
+        for t in range(lo, hi):
+            s, o = int(sb[t]), int(ob[t])
+            rb = sr.RayBoard(bs, s, o)
+            lg = rb.legal()
+            assert int(lb[t]) == lg, "plane 2 is the standard legal mask"
+            assert not (lg == 0 and rb.legal(-1) == 0), "a recorded position is not terminal"
+            legal = [a for a in range(cells) if (lg >> a) & 1] or [cells]
+            passes += legal == [cells]
+            pi = pis[t]
+            assert all(pi[a] == 0 for a in range(cells + 1) if a not in legal), "pi is zero off the legal set"
+            assert abs(float(pi.astype(np.float64).sum()) - 1.0) < 1e-6
+            succ = {}
+            for a in legal:
+                if pi[a] > 0:
+                    nb = sr.RayBoard(bs, s, o)
+                    assert nb.make_move(a)
+                    succ[nb.bits()] = nb
+            if t + 1 < hi:      # linked to the next recorded state by a standard-legal move (or the pass) with pi > 0
+                assert (int(sb[t + 1]), int(ob[t + 1])) in succ, "game %d ply %d: no legal move leads to the next state" % (g, t - lo)
+            else:               # the last ply: the game ends exactly at a standard-terminal position
+                ends = [nb for nb in succ.values() if nb.is_terminal()]
+                assert ends, "game %d: its last move does not end the game" % g
+                winners = {nb.winner() for nb in ends}
+        # z = winner (relative to the side to move at the end) x (+1 on even plies, -1 on odd)   [L16]
+        z = zs[lo:hi]
+        sign = np.array([1.0 if (t - lo) % 2 == 0 else -1.0 for t in range(lo, hi)], dtype=np.float32)
+        assert any(np.array_equal(z, np.float32(w) * sign) for w in winners), "game %d: z" % g
+    return passes
+
+
+def test_selfplay_worker_on_standard_rules(pkg):
+    torch.manual_seed(3)
+    net = pkg.OthelloResNet(2, 16).eval()
+    kw = dict(num_simulations=6, temperature_threshold=8, num_parallel_games=8, verbose=False, lanes=1)
+    w = pkg.ParallelSelfPlayWorker(pkg.StandardOthelloBitboard, net, **kw)
+    assert w.rules == "othello" and w.engine.rules == "othello" and w.rng_mode == "device"
+    np.random.seed(5)
+    data = w.execute_episodes(12)
+    assert w.engine.rules == "othello"              # (the engine a 12-game call grows is on the same rules)
+    states = np.stack([d[0] for d in data])
+    pis = np.stack([d[1] for d in data])
+    zs = np.array([d[2] for d in data], dtype=np.float32)
+    check_stream(8, states, pis, zs, 12)
+    np.random.seed(5)
+    again = w.execute_episodes(12)
+    assert len(again) == len(data) and all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+                                           for a, b in zip(again, data))
+    # rules="reference" through the worker == the engine at default arguments (what the parent commit runs), same seed
+    q = pkg.ParallelSelfPlayWorker(pkg.OthelloBitboard, net, **kw)
+    assert q.rules == "reference" and q.engine.rules == "reference"
+    got = q.execute_episodes_arrays(12, seed=99)
+    eng = pkg.SearchEngine(q.engine.max_games, 6, temperature_threshold=8, evaluator=q.batch_mcts.evaluator)
+    n = eng.selfplay_run(12, 99)
+    want = eng.selfplay_fetch(n)[:3]
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    other = w.execute_episodes_arrays(12, seed=99)
+    assert not (other[0].shape == want[0].shape and np.array_equal(other[0], want[0]))   # the rule sets play other games
+
+
+def stream_of(data):
+    return (np.stack([d[0] for d in data]), np.stack([d[1] for d in data]), np.array([d[2] for d in data], dtype=np.float32))
+
+
+def test_other_worker_modes_follow_the_board_class(pkg):
+    """The numpy-RNG mode (its host mirror boards draw the random numbers: a mirror on other rules than the engine's would
+    leave the games out of step) and the serial SelfPlayWorker in both of its modes."""
+    torch.manual_seed(6)
+    net = pkg.OthelloResNet(2, 16).eval()
+    np.random.seed(11)
+    w = pkg.ParallelSelfPlayWorker(pkg.StandardOthelloBitboard, net, num_simulations=6, temperature_threshold=8,
+                                   num_parallel_games=4, verbose=False, rng_mode="numpy")
+    check_stream(8, *stream_of(w.execute_episodes(4, add_dirichlet_noise=True)), 4)
+    mcts = pkg.MCTS(net)
+    for mode, games in (("device", 5), ("numpy", 1)):
+        sw = pkg.SelfPlayWorker(pkg.StandardOthelloBitboard, mcts, num_simulations=6, temperature_threshold=8, rng_mode=mode)
+        assert sw.rules == "othello"
+        check_stream(8, *stream_of(sw.execute_episodes(games)), games)
+    assert sw._engine is None and {k[2] for k in mcts._engines} == {"othello"}
+
+
+def test_selfplay_engine_6x6_on_standard_rules(pkg):
+    torch.manual_seed(4)
+    net = pkg.OthelloResNet(2, 16, board_size=6).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    eng = pkg.SearchEngine(8, 6, temperature_threshold=6, evaluator=ev, rules="othello")
+    assert eng.board_size == 6
+    n = eng.selfplay_run(12, 31)
+    st, pi, z, gl = eng.selfplay_fetch(n)
+    assert n == gl.sum() and 20 <= gl.min() and gl.max() <= 40
+    check_stream(6, st, pi, z, 12, gl)
+    n2 = eng.selfplay_run(12, 31)
+    for a, b in zip(eng.selfplay_fetch(n2), (st, pi, z, gl)):
+        assert np.array_equal(a, b)
+
+
+# ---- 6. lock-step exactness ----------------------------------------------------------------------------------------
+def hip_eval_fn(ev, cap, bs):
+    """eval_fn of py_search whose answers are the HIP network's own: one position in a launch of `cap` rows (the shape the
+    engine launches), priors through oth_policy_exp (the engine's expf).  Memoised per position."""
+    memo = {}
+
+    def fn(s, o, lg):
+        if (s, o) not in memo:
+            ss, oo, ll = (np.zeros(cap, dtype=U64) for _ in range(3))
+            ss[0], oo[0], ll[0] = s, o, lg
+            logp, v = ev.forward_bits(dev_u64(ss), dev_u64(oo), dev_u64(ll))
+            memo[(s, o)] = (ev.policy_probs(logp)[0].cpu().numpy(), float(v[0, 0].cpu()))
+        return memo[(s, o)]
+    return fn
+
+
+def test_lockstep_selfplay_pi_equals_the_python_search(pkg):
+    torch.manual_seed(8)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    sims, games = 6, 4
+    eng = pkg.SearchEngine(games, sims, temperature_threshold=8, evaluator=ev, rules="othello")
+    rules = sr.RayRules(8)
+    fn = hip_eval_fn(ev, games, 8)
+    pos = [sr.start_position(8)] * games
+    over = [False] * games                               # (a standard game can end early; none is expected to in 12 plies)
+    plies = [0] * games
+    rng = np.random.Generator(np.random.PCG64(2))
+    eng.selfplay_begin(games)
+    for ply in range(12):
+        pi, active = eng.selfplay_search()
+        assert active.tolist() == [0 if f else 1 for f in over]
+        actions = np.zeros(games, dtype=np.int32)
+        for i, (s, o) in enumerate(pos):
+            if over[i]:
+                continue
+            _, _, _, want = sr.py_search(rules, s, o, sims, 1.0, fn)
+            assert np.array_equal(pi[i], want), "game %d ply %d" % (i, ply)
+            moves = np.flatnonzero(pi[i] > 0)            # different games take different lines
+            a = int(moves[int(rng.integers(len(moves)))])
+            assert a in sr.legal_actions(rules, s, o)
+            actions[i], plies[i] = a, plies[i] + 1
+            pos[i] = s, o = sr.apply_move(rules, s, o, a)
+            over[i] = rules.legal(s, o) == 0 and rules.legal(o, s) == 0
+        assert eng.selfplay_apply(actions) == over.count(False)
+    n = eng.selfplay_end()
+    st, p, z, gl = eng.selfplay_fetch(n)
+    # (a lock-step run harvests the games that ENDED; the ones still in progress have length 0 and no tuples)
+    assert sum(plies) > 40 and gl.tolist() == [p_ if f else 0 for p_, f in zip(plies, over)] and n == int(gl.sum())
+
+
+# ---- 7. arena / best action ----------------------------------------------------------------------------------------
+def test_best_action_on_standard_boards(pkg):
+    roots = sr.search_roots(8, STD, 8)
+    boards = []
+    for s, o in roots:
+        b = pkg.StandardOthelloBitboard()
+        b.self_board, b.opp_board = s, o
+        boards.append(b)
+    rules = sr.RayRules(8)
+    sims = 20
+
+    def choice(s, o, fn):
+        visits = sr.py_search(rules, s, o, sims, 1.0, fn)[0]
+        legal = sr.legal_actions(rules, s, o)
+        return legal[int(np.argmax([visits[a] for a in legal]))]     # first maximum, as np.argmax over the children
+
+    # the batched search BatchedArena makes its moves with, under the stub evaluator
+    class Stub:
+        host_eval = staticmethod(stub_host_eval(65))
+    bm = pkg.BatchMCTS(None, evaluator=Stub())
+    res = bm.search_batch(boards, sims, temperature=0.0)
+    fn = sr.stub_eval_fn(65)
+    from othello_reinforcement_learning_test_amd.mcts import best_action_from_policy
+    for b, (pi, _) in zip(boards, res):
+        a = best_action_from_policy(pi, b.get_legal_moves())
+        assert a in sr.legal_actions(rules, b.self_board, b.opp_board)
+        assert a == choice(b.self_board, b.opp_board, fn)
+    with pytest.raises(ValueError, match="different rule sets"):
+        bm.search_batch([boards[0], pkg.OthelloBitboard()], sims)
+    # MCTS.get_best_action (what MCTSPlayer / Arena call) on the HIP network: the engine follows the board's rule set
+    torch.manual_seed(9)
+    mcts = pkg.MCTS(pkg.OthelloResNet(2, 16).eval())
+    hfn = hip_eval_fn(mcts.evaluator, 1, 8)
+    for b in boards:
+        a = mcts.get_best_action(b, sims)
+        assert a in sr.legal_actions(rules, b.self_board, b.opp_board)
+        assert a == choice(b.self_board, b.opp_board, hfn)
+    assert {k[2] for k in mcts._engines} == {"othello"}
+    q = pkg.OthelloBitboard()
+    assert mcts.get_best_action(q, sims) in q.get_legal_moves() and {k[2] for k in mcts._engines} == {"othello", "reference"}
