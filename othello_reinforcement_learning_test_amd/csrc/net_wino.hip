@@ -13,13 +13,20 @@
 //   M_xi = sum over (row tap dy, input channel) of U[dy][xi] V[xi](row y+dy);  y0 = M0+M1+M2, y1 = M1-M2-M3
 //
 // One 512-thread workgroup (8 waves) per CU carries TWO positions through the whole network.  Wave w owns output
-// channels [16w, 16w+16) of both positions: 4 N-tiles of 16 Winograd tiles (position p, board half h: rows 4h..4h+3 x
-// tile column j) x 4 transformed taps = 16 accumulators.  The MFMA result keeps the tile on the lane and the four xi in
-// four accumulators, so the OUTPUT transform is in-lane; the INPUT transform of the next layer needs in(2j-1) and
-// in(2j+2) from the neighbouring tile columns = the neighbouring lanes of a quad (DPP quad_perm), in registers too.  The
-// transformed operand V lives in LDS as [position][tile 0..31][xi][hi 128 x f16 | lo 128 x f16] = 128 KB (the reason
-// for one workgroup per CU), 16-byte chunks XOR-swizzled with the tile index so that every ds_read_b128 lane group is
-// conflict-free; a row tap is a shift of 4 tiles; out-of-board rows read a zero block.
+// channels [16w, 16w+16) of both positions: 4 N-tiles of 16 Winograd tiles (position p, row parity: the even rows
+// 0,2,4,6 or the odd rows 1,3,5,7 x tile column j) x 4 transformed taps = 16 accumulators.  The MFMA result keeps the
+// tile on the lane and the four xi in four accumulators, so the OUTPUT transform is in-lane; the INPUT transform of the
+// next layer needs in(2j-1) and in(2j+2) from the neighbouring tile columns = the neighbouring lanes of a quad (DPP
+// quad_perm), in registers too.  The transformed operand V lives in LDS as [position][tile 0..31 = row*4 + j][xi]
+// [hi 128 x f16 | lo 128 x f16] = 128 KB (the reason for one workgroup per CU), 16-byte chunks XOR-swizzled with
+// (row >> 1)*4 + j so that every ds_read_b128 lane group is conflict-free (tools/lds_bank_model.py); out-of-board rows
+// read a zero block.
+//
+// Why row parity: the B operand of (N-tile, row tap dy) is the four rows {2*r + parity + dy}.  Over the two N-tiles of a
+// position and the three row taps that is only FOUR different fragments -- F0 = rows {-1,1,3,5}, F1 = {0,2,4,6},
+// F2 = {1,3,5,7}, F3 = {2,4,6,8}: even rows use F0 F1 F2, odd rows F1 F2 F3, lane for lane the same rows -- so a
+// (k-step, xi, position) reads 4 operand pairs from LDS for its 18 MFMAs.  With board halves as N-tiles the six
+// (N-tile, row tap) fragments were all different: 384 ds_read_b128 per wave and layer; now 256.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,7 +53,7 @@ constexpr float kWClamp = 30000.0f;           // |V| <= 2 x (activation x act_sc
 
 struct WinoWeights {
     int blocks = 0;
-    uint4* d_w = nullptr;     // [layer][dy 3][kk 4][wave 8][xi 4][hi, lo][64 lanes] x 16 B   (A fragments of U)
+    uint4* d_w = nullptr;     // [layer][kk 4][xi 4][wave 8][dy 3][hi, lo][64 lanes] x 16 B   (A fragments of U)
     uint4* d_stem = nullptr;  // [wave 8][hi, lo][64 lanes] x 16 B: direct 3x3 stem as one k-step of 32 (27 used)
     float* d_bias = nullptr;  // [1 + 2*blocks][128], x act_scale (register_scaled_bias)
     float* d_inv = nullptr;   // [1 + 2*blocks] 1 / weight scale
@@ -226,13 +233,14 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
         const int64_t k = *n_valid;
         nv = k < n ? k : n;
     }
-    constexpr int NT = 2 * TP;   // N-tiles of a wave: (position, board half)
+    constexpr int NT = 2 * TP;   // N-tiles of a wave: (position, row parity)
     const int64_t pos0 = (int64_t)blockIdx.x * TP;   // a workgroup takes position group blockIdx.x
     if (pos0 >= nv) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g4 = lane >> 4, c = lane & 15;
-    const int row4 = c >> 2, j = c & 3;        // row within the board half, tile column
-    // N-tile nt = 2*p + h: position p, board half h; this lane's tile index within the position: 16*h + c
+    const int row4 = c >> 2, j = c & 3;        // row pair, tile column
+    // N-tile nt = 2*p + parity: position p, even or odd rows; this lane's cell row is 2*row4 + parity, its tile index
+    // within the position (2*row4 + parity)*4 + j
 
     // ---- stem input: im2col of the three bit planes, [128 cells][32 k] f16 (64 B per cell) at LDS 0 (V is not live yet)
     if (tid < TP * 64) {
@@ -288,7 +296,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const int cell = (nt >> 1) * 64 + ((nt & 1) * 4 + row4) * 8 + 2 * j + e;
+                const int cell = (nt >> 1) * 64 + (2 * row4 + (nt & 1)) * 8 + 2 * j + e;
                 const half8 xh = *(const half8*)(lds + cell * 64 + g4 * 16);
                 acc[3 * e][nt] = wmfma(wlo, xh, acc[3 * e][nt]);
                 acc[3 * e][nt] = wmfma(wh, xh, acc[3 * e][nt]);
@@ -301,33 +309,36 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
     uint32_t wr_off[NT];                                                  // store address of (N-tile, xi = 0), hi part
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const uint32_t tl = (uint32_t)((nt & 1) * 16 + c);
-        wr_off[nt] = ((uint32_t)(nt >> 1) * 32 + tl) * (4 * kWTile) + ((wchunk ^ (tl & 15)) << 4) + 8u * (uint32_t)(g4 & 1);
+        // the swizzle key of a tile is (row >> 1)*4 + j: this lane's c for both of its N-tiles
+        const uint32_t tl = (uint32_t)((2 * row4 + (nt & 1)) * 4 + j);
+        wr_off[nt] = ((uint32_t)(nt >> 1) * 32 + tl) * (4 * kWTile) + ((wchunk ^ (uint32_t)c) << 4) + 8u * (uint32_t)(g4 & 1);
     }
-    uint32_t rd_base[NT][3];  // read base of (N-tile, row tap): the tile 4*dy further, or the zero block
-    uint32_t rd_key[3];       // (source tile & 15) << 4, xor-ed with the k-group chunk
+    uint32_t rd_base[TP][4];  // read base of (position, fragment f): this lane's row 2*row4 + f - 1, or the zero block
+    uint32_t rd_key[4];       // (key of the source tile) << 4, xor-ed with the k-group chunk: c - 4, c, c, c + 4
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        rd_key[d] = ((uint32_t)((c + 4 * (d - 1)) & 15) << 4) ^ ((uint32_t)g4 << 4);
+    for (int f = 0; f < 4; ++f) {
+        const int y = 2 * row4 + f - 1;
+        rd_key[f] = ((uint32_t)(((y >> 1) * 4 + j) & 15) << 4) ^ ((uint32_t)g4 << 4);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int y = (nt & 1) * 4 + row4 + (d - 1);
-            const int ts = (nt & 1) * 16 + c + 4 * (d - 1);
-            rd_base[nt][d] = (y >= 0 && y < 8) ? (uint32_t)((nt >> 1) * 32 + ts) * (4 * kWTile) : (uint32_t)kWZeroOff;
-        }
+        for (int p = 0; p < TP; ++p)
+            rd_base[p][f] = (y >= 0 && y < 8) ? (uint32_t)(p * 32 + y * 4 + j) * (4 * kWTile) : (uint32_t)kWZeroOff;
     }
     const float mask_l = j == 0 ? 0.f : 1.f, mask_r = j == 3 ? 0.f : 1.f;
     const f32x2 mask_l2 = {mask_l, mask_l}, mask_r2 = {mask_r, mask_r};
 
     const int n_layers = 1 + a.n_res_layers;
     uint32_t sat_bits = 0;
-    // weight ring: [group mod RING][xi hi, xi lo]; a group = (row tap, k-step): 8 fragments.  Two groups at TP = 2; FOUR
-    // at TP = 1, where the launch is one position per CU and bound by how many bytes of the weight stream (15.7 MB per
-    // forward through ONE CU's vector-memory path), not by MFMAs: one position 0.177 -> 0.172 ms with 3 or 4 groups in flight
-    // (6 spills: 0.259); the same loads with the non-temporal hint: 0.258 ms (they lose their L2 hits)
-    constexpr int RING = TP == 1 ? 4 : 2;
-    static_assert(12 % RING == 0, "the ring index must be a compile-time function of the group");
-    uint4 wq[RING][8];
+    // weight ring: a group = (k-step, xi) carries 6 fragments (row tap dy x hi, lo); fragment F = 6*group + 2*dy + hi/lo
+    // of a wave's stream lives in wq[F mod NRING] and is requested LA fragments ahead of its group's first step.  Two
+    // groups at TP = 2 (12 slots, 6 ahead); 32 slots with 26 ahead at TP = 1, where the launch is one position per CU
+    // and bound by how many bytes of the weight stream (15.7 MB per forward through ONE CU's vector-memory path), not
+    // by MFMAs: one position 0.177 -> 0.172 ms with 24 or 32 fragments in flight (6 spills: 0.259); the same loads with
+    // the non-temporal hint: 0.258 ms (they lose their L2 hits)
+    constexpr int NG = 16;                       // groups of a layer
+    constexpr int NRING = TP == 1 ? 32 : 12;
+    constexpr int LA = NRING - 6;                // the slot of fragment F + LA held a fragment of the previous group
+    static_assert((NG * 6) % NRING == 0, "the ring slot must be a compile-time function of (group, fragment)");
+    uint4 wq[NRING];
 #ifdef OTH_STAMPS
     unsigned long long ph_[4] = {0, 0, 0, 0}, t0_ = w_clk(), tstart_ = t0_;
     const unsigned long long rstart_ = w_realclk();
@@ -341,8 +352,9 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
             inv = invn;
         }
         const f32x2 inv2 = {inv, inv};
-        // A fragments of conv `layer+1`: group g = dy*4 + kk at wl + g * (8 waves * 8 frags * 64) uint4
-        const uint4* wl = a.w + (size_t)layer * (12 * 8 * 8 * 64) + (size_t)wave * (8 * 64) + lane;
+        // A fragments of conv `layer+1`: group g = kk*4 + xi at wl + g * (8 waves * 6 frags * 64) uint4
+        const uint4* wl = a.w + (size_t)layer * (NG * 8 * 6 * 64) + (size_t)wave * (6 * 64) + lane;
+        auto wfrag = [&](int F) -> const uint4* { return wl + (size_t)(F / 6) * (8 * 6 * 64) + (size_t)(F % 6) * 64; };
         // ---------------- epilogue of conv `layer`: output transform, scale, bias, skip, ReLU; then the next layer's
         //                  input transform and the hi/lo re-split into V
         // Two variants only -- SKIP (even layers: the stem, where the residual registers hold zeros, and the second
@@ -417,12 +429,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
         // cycles + 2 LDS reads + address VALU ~ 48 of its 48 cycles), so the extra VALU is not hidden, it slows the
         // partner's convolution.  Tried again with the arithmetic at s_setprio 0 and the convolution at s_setprio 3, whole
         // and for one or two N-tiles only: 3.60 / 2.94 / 3.04 ms -- the 16-64 extra live VGPRs spill at the 256 limit.)
-        if (layer == 0 && !last) {   // the first weight group of the first convolution; the later ones load theirs in
-                                     // the previous convolution's last group
+        if (layer == 0 && !last) {   // the first LA fragments of the first convolution; the later ones load theirs in
+                                     // the previous convolution's last groups
 #pragma unroll
-            for (int g = 0; g < RING - 1; ++g)
-#pragma unroll
-                for (int f = 0; f < 8; ++f) wq[g][f] = wl[(size_t)g * (8 * 8 * 64) + (size_t)f * 64];
+            for (int F = 0; F < LA; ++F) wq[F] = *wfrag(F);
         }
         OTH_WSTAMP(0)
         wbarrier();   // every wave has finished reading V (or the stem's im2col)
@@ -434,70 +444,80 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
         wbarrier();
         OTH_WSTAMP(1)
 
-        // ---------------- conv `layer+1` in the Winograd domain: 12 groups (row tap d, k-step kk) x 16 steps (N-tile,
-        // xi) x 3 split products.  One straight-line software pipeline over all 192 steps: the two LDS reads of step
-        // q+2 and, spread over a group, the eight weight loads of the next group sit between the MFMAs.
+        // ---------------- conv `layer+1` in the Winograd domain: 16 groups (k-step kk, xi) x TP positions x 6 steps
+        // (accumulator, row tap) x 3 split products.  A position's six steps of a group, fragments F0..F3 read once each:
+        //   E += U[-1] F0;  E += U[0] F1;  O += U[-1] F1;  E += U[+1] F2;  O += U[0] F2;  O += U[+1] F3
+        // (E / O: the even- / odd-row accumulator of this xi), so every accumulator sums (kk outer, row tap inner) in both
+        // builds.  One straight-line software pipeline over all 16 * TP * 6 steps: the two LDS reads of the operand pair
+        // PD pairs ahead sit in the step that first uses a pair (4 of a position's 6 steps) and, spread over a group's
+        // first six steps, the six weight loads of a later group sit between the MFMAs.
         // (Tried with the 30 registers the leaner epilogue freed: LDS prefetch distance 3 and 4, and the two waves of a SIMD
         // taking turns at s_setprio 2 group by group, to even out the oldest-first arbitration that lets one of them
         // finish its convolution ~8 k cycles before the other: 2.561-2.578 vs 2.562 ms -- no change.)
-        // step q = ((d*4 + kk)*4 + nt)*4 + xi.  (Tried: xi as the outer index of a group with ONE 8-fragment weight ring --
+        // (Tried, with groups of (row tap, k-step): xi as the outer index of a group with ONE 8-fragment weight ring --
         // the pair of (group, xi) reloaded right after its fourth use -- and per-use address arithmetic instead of the
         // hoisted (key ^ k-step) values: 32 VGPRs fewer, no spill, but 2.88 vs 2.69 ms: the extra VALU per step costs more
         // issue slots than the registers were worth.)
-        constexpr int GS = NT * 4;          // steps of a group: (N-tile, xi)
-        constexpr int QT = 12 * GS;         // steps of a layer
-        auto src_of = [&](int q) -> const char* {
-            const int xi = q & 3, nt = (q >> 2) % NT, grp = q / GS, kk = grp & 3, d = grp >> 2;
-            return lds + rd_base[nt][d] + ((uint32_t)(kk << 6) ^ rd_key[d]) + xi * kWTile;
+        constexpr int GS = TP * 6;          // steps of a group: (position, accumulator x row tap)
+        constexpr int NO = NG * TP * 4;     // operand pairs of a layer: (group, position, fragment)
+        auto src_of = [&](int o) -> const char* {
+            const int f = o & 3, p = (o >> 2) % TP, grp = o / (4 * TP), xi = grp & 3, kk = grp >> 2;
+            return lds + rd_base[p][f] + ((uint32_t)(kk << 6) ^ rd_key[f]) + xi * kWTile;
         };
-        constexpr int PD = 2;   // LDS operand pairs in flight ahead of the MFMAs (steps)
+        constexpr int PD = 2;   // LDS operand pairs in flight ahead of the MFMAs
         half8 xh[PD + 1], xl[PD + 1];
 #pragma unroll
-        for (int q = 0; q < PD; ++q) {
-            xh[q] = *(const half8*)src_of(q);
-            xl[q] = *(const half8*)(src_of(q) + 256);
+        for (int o = 0; o < PD; ++o) {
+            xh[o] = *(const half8*)src_of(o);
+            xl[o] = *(const half8*)(src_of(o) + 256);
         }
-        // one instantiation per row tap (4 groups of straight-line code each, like k_trunk16's tap rows): a single loop
+        // one instantiation per k-step (4 groups of straight-line code each, like k_trunk16's tap rows): a single loop
         // over the whole layer is beyond what hipcc unrolls, and a rolled loop turns every register array into
         // v_cndmask / v_readlane select chains
-        auto conv_d = [&](auto DC) {
-            constexpr int D = decltype(DC)::value;
+        auto conv_k = [&](auto KC) {
+            constexpr int K = decltype(KC)::value;
 #pragma unroll
             for (int ql = 0; ql < 4 * GS; ++ql) {
-                const int q = D * 4 * GS + ql;
-                const int xi = q & 3, nt = (q >> 2) % NT, grp = q / GS, sl = q % (PD + 1), psl = (q + PD) % (PD + 1);
-                const int step = q % GS;                       // within the group
-                const half8 wh = __builtin_bit_cast(half8, wq[grp % RING][2 * xi]);
-                const half8 wlo = __builtin_bit_cast(half8, wq[grp % RING][2 * xi + 1]);
+                const int q = K * 4 * GS + ql;
+                const int grp = q / GS, step = q % GS, xi = grp & 3;   // step within the group
+                const int p = step / 6, s = step % 6;
+                const int f = (s + 1) >> 1, par = (0x34 >> s) & 1, d = f - par;   // fragment 0 1 1 2 2 3, rows E E O E O O
+                const int nt = 2 * p + par;
+                const int o = (grp * TP + p) * 4 + f, sl = o % (PD + 1), psl = (o + PD) % (PD + 1);
+                const bool fetch = ((0x2B >> s) & 1) && o + PD < NO;   // steps 0 1 3 5: the first use of pair o, so the
+                                                                       // last use of pair o - 1, whose slot o + PD takes
+                const half8 wh = __builtin_bit_cast(half8, wq[(grp * 6 + 2 * d) % NRING]);
+                const half8 wlo = __builtin_bit_cast(half8, wq[(grp * 6 + 2 * d + 1) % NRING]);
                 OTH_WSB;
-                if (q < GS) acc[xi][nt] = wmfma0(wh, xl[sl]);     // the layer's first group starts every accumulator
+                if (grp < 4 && d == 0) acc[xi][nt] = wmfma0(wh, xl[sl]);   // k-step 0, first row tap starts an accumulator
                 else acc[xi][nt] = wmfma(wh, xl[sl], acc[xi][nt]);
                 OTH_WSB;
-                if (q + PD < QT) xh[psl] = *(const half8*)src_of(q + PD);
+                if (fetch) xh[psl] = *(const half8*)src_of(o + PD);
                 OTH_WSB;
                 acc[xi][nt] = wmfma(wh, xh[sl], acc[xi][nt]);
                 OTH_WSB;
-                if (q + PD < QT) xl[psl] = *(const half8*)(src_of(q + PD) + 256);
-                // next group's fragments, one per step, as early as the ring allows (its other half is free from the
-                // group's first step on): at TP = 2 that is >= 8 steps = 770+ cycles of cover for the L2 latency (issued
-                // at steps 4..11 both waves of a SIMD stalled ~300 cycles at every group boundary)
-                // (grp = 11 loads group 0 of the NEXT convolution -- the layers are contiguous, and one zero group pads the
-                // end of the array for the last one: issued together before the barrier instead, the eight waves' 64 KB
-                // burst through the CU's one 64 B/clk vector-memory path held every wave for ~1.1 k cycles per layer)
-                if (grp == 10 && step == GS / 2) {
+                if (fetch) xl[psl] = *(const half8*)(src_of(o + PD) + 256);
+                // a later group's fragments, one per step, as early as the ring allows (the slots of the previous group
+                // are free from this group's first step on): at TP = 2 that is >= 6 steps = 580+ cycles of cover for
+                // the L2 latency (issued in the group's second half both waves of a SIMD stalled ~300 cycles at every
+                // group boundary)
+                // (the last groups load the first fragments of the NEXT convolution -- the layers are contiguous, and zero
+                // groups pad the end of the array for the last one: issued together before the barrier instead, the eight
+                // waves' burst through the CU's one 64 B/clk vector-memory path held every wave for ~1.1 k cycles per layer)
+                if (grp == NG - 2 && step == GS / 2) {
                     b4n = *(const float4*)(a.bias + (layer + 1) * 128 + ch0);
                     invn = a.inv[layer + 1];
                 }
-                if (step < 8)
-                    wq[(grp + RING - 1) % RING][step] = wl[(size_t)(grp + RING - 1) * (8 * 8 * 64) + (size_t)step * 64];
+                if (step < 6) wq[(grp * 6 + step + LA) % NRING] = *wfrag(grp * 6 + step + LA);
                 OTH_WSB;
                 acc[xi][nt] = wmfma(wlo, xh[sl], acc[xi][nt]);
                 OTH_WSB;
             }
         };
-        conv_d(std::integral_constant<int, 0>{});
-        conv_d(std::integral_constant<int, 1>{});
-        conv_d(std::integral_constant<int, 2>{});
+        conv_k(std::integral_constant<int, 0>{});
+        conv_k(std::integral_constant<int, 1>{});
+        conv_k(std::integral_constant<int, 2>{});
+        conv_k(std::integral_constant<int, 3>{});
         OTH_WSTAMP(3)
     }
 #ifdef OTH_STAMPS
@@ -520,7 +540,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const int cell = (nt >> 1) * 64 + ((nt & 1) * 4 + row4) * 8 + 2 * j + e;
+            const int cell = (nt >> 1) * 64 + (2 * row4 + (nt & 1)) * 8 + 2 * j + e;
             const float us = 1.0f / a.act_scale;
             const f32x4 v = res[nt][e];
             float* dst = (float*)lds + (size_t)cell * kHeadRow + ch0;   // odd row stride: four scalar stores
@@ -579,8 +599,9 @@ int wino_pack_weights(oth_net* net) {
     ww->blocks = hn.blocks;
     net->wino = ww;
     const size_t frag = 64 * 8;                              // halfs per fragment
-    const size_t layer_halfs = (size_t)12 * 8 * 8 * frag;    // 12 groups x 8 waves x (4 xi x hi/lo)
-    std::vector<uint16_t> w((size_t)L * layer_halfs + 5 * 8 * 8 * frag), stem((size_t)8 * 2 * frag);   // + zero groups: the last conv's look-ahead (ring depth - 1, at most 5)
+    const size_t layer_halfs = (size_t)16 * 8 * 6 * frag;    // 16 groups (kk, xi) x 8 waves x (3 dy x hi/lo): the order the
+                                                             // kernel streams them in, one ascending run per wave
+    std::vector<uint16_t> w((size_t)L * layer_halfs + 6 * 8 * 6 * frag), stem((size_t)8 * 2 * frag);   // + zero groups: the last conv's look-ahead (at most 31 fragments = 6 groups)
     std::vector<float> bias((size_t)(L + 1) * 128), inv(L + 1);
     {   // stem: direct, gemm k = tap*3 + plane (27 of 32), rows = 16 channels of a wave
         const FoldedConv& cv = hn.stem;
@@ -629,7 +650,7 @@ int wino_pack_weights(oth_net* net) {
                                 const float v = (float)(U[(((size_t)d * 4 + xi) * 128 + ci) * 128 + co] * scale);
                                 uint16_t hi, lo;
                                 wsplit(v, hi, lo);
-                                const size_t f0 = (size_t)li * layer_halfs + ((((size_t)(d * 4 + kk) * 8 + wv) * 4 + xi) * 2) * frag;
+                                const size_t f0 = (size_t)li * layer_halfs + ((((size_t)(kk * 4 + xi) * 8 + wv) * 3 + d) * 2) * frag;
                                 w[f0 + (size_t)l * 8 + jj] = hi;
                                 w[f0 + frag + (size_t)l * 8 + jj] = lo;
                             }

@@ -10,7 +10,7 @@ out=gpurun_out/pmc_bench
 rm -rf "$out"; mkdir -p "$out"
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum"; do
   set -- $pass; name=$1; shift
-  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/$name" -o "$name" -- $CMD > "$out/$name.json" 2> "$out/$name.err" || { tail -5 "$out/$name.err"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/$name" -o "$name" -- $CMD > "$out/$name.json" 2> "$out/$name.err" || { tail -5 "$out/$name.err"; exit 1; }
   python3 tools/pmc_summary.py "$out/$name" --all | sed "s|^$out/||" >> "$out/summary.txt"
 done
 cat "$out/summary.txt"

@@ -13,19 +13,19 @@ import sys
 
 ABLATIONS = {
     # ---- k_trunk_w (net_wino.hip), round 3: what is left is power, not issue slots -------------------------------------
-    "wino_halflds": ("every second conv step reuses stale operand registers instead of reading LDS (WRONG results)", [
-        ("net_wino.hip", "                if (q + PD < QT) xh[psl] = *(const half8*)src_of(q + PD);",
-         "                if (q + PD < QT && ((q + PD) & 1) == 0) xh[psl] = *(const half8*)src_of(q + PD);"),
-        ("net_wino.hip", "                if (q + PD < QT) xl[psl] = *(const half8*)(src_of(q + PD) + 256);",
-         "                if (q + PD < QT && ((q + PD) & 1) == 0) xl[psl] = *(const half8*)(src_of(q + PD) + 256);"),
+    "wino_halflds": ("every second operand pair reuses stale registers instead of reading LDS (WRONG results)", [
+        ("net_wino.hip", "                if (fetch) xh[psl] = *(const half8*)src_of(o + PD);",
+         "                if (fetch && ((o + PD) & 1) == 0) xh[psl] = *(const half8*)src_of(o + PD);"),
+        ("net_wino.hip", "                if (fetch) xl[psl] = *(const half8*)(src_of(o + PD) + 256);",
+         "                if (fetch && ((o + PD) & 1) == 0) xl[psl] = *(const half8*)(src_of(o + PD) + 256);"),
     ]),
     "wino_nowrite": ("no V stores in the epilogue; the values stay live through a dummy use (WRONG results)", [
         ("net_wino.hip", "                        *(uint2*)dst = hi;\n                        *(uint2*)(dst + 256) = lo;",
          '                        asm volatile("" :: "v"(hi), "v"(lo), "v"(dst));'),
     ]),
     "wino_halfw": ("every second weight fragment keeps its stale registers: half the L2 -> CU stream (WRONG results)", [
-        ("net_wino.hip", "                if (step < 8)\n                    wq[(grp + RING - 1) % RING][step] =",
-         "                if (step < 8 && (step & 1) == 0)\n                    wq[(grp + RING - 1) % RING][step] ="),
+        ("net_wino.hip", "                if (step < 6) wq[(grp * 6 + step + LA) % NRING] =",
+         "                if (step < 6 && (step & 1) == 0) wq[(grp * 6 + step + LA) % NRING] ="),
     ]),
     "wino_nosat": ("no saturation tracking in the epilogue (clamped activations would go unreported)", [
         ("net_wino.hip", "                sat_bits = max(sat_bits, max(max(__float_as_uint(v0[0].x), __float_as_uint(v0[0].y)),\n"
