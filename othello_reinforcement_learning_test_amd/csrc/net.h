@@ -1,5 +1,7 @@
-// net.h -- evaluator object shared by net.hip (API, weight folding), net_f32.hip (exact-fp32 MFMA trunk, every
-// width and board size) and net_mfma.hip (the fp16-split MFMA trunk for 128 filters).
+// net.h -- the evaluator object and the trunk table.  net.hip owns the API, the weight folding, the head parameters and
+// the table's rows in priority order; every trunk file (net_f32.hip with net_f32c.hip, net_wino6.hip, net_wino.hip,
+// net_h3.hip, net_mfma.hip) defines one TrunkImpl row: its kernels, weight packing, launch and what kernel_info reports.
+// net_pack.h holds the host helpers the packers share.
 #pragma once
 #include <vector>
 
@@ -28,7 +30,7 @@ struct HostNet {
     std::vector<float> vfc2_w, vfc2_b;  // [256], [1]        (net.py:117)
 };
 
-// device-side parameter block of the heads (fp32, shared by both trunk kernels)
+// device-side parameter block of the heads (fp32, shared by every trunk kernel)
 struct HeadParams {
     const float* pconv_w;  // [F][2]
     const float* pconv_b;  // [2]
@@ -42,11 +44,25 @@ struct HeadParams {
     const float* vfc2_b;   // [1]
 };
 
-struct MfmaWeights;  // net_mfma.hip
-struct F32Weights;   // net_f32.hip
-struct H3Weights;    // net_h3.hip
-struct WinoWeights;  // net_wino.hip
-struct Wino6Weights; // net_wino6.hip
+// One row of the trunk table (net.hip: kTrunks).  oth_net_load_state takes the first row that serves the network, packs
+// that row's weights only and keeps the row; oth_net_forward_bits and oth_net_kernel_info call through it.
+struct TrunkImpl {
+    // does this trunk run `net` at `precision` (OTH_PREC_*)?  Reads the A/B switch of its row, if it has one.
+    bool (*serves)(const oth_net* net, int precision);
+    // weights in the kernel's fragment order -> net->trunk_w (set before the first upload: destroy frees a partial pack)
+    int (*pack)(oth_net* net);
+    void (*destroy)(void* weights);
+    int (*forward)(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
+                   const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
+    // the kernel a launch of n positions runs, MFMA FLOPs issued per algorithmic FLOP, activation clamp (0: none)
+    void (*info)(const oth_net* net, int64_t n, const char** name, double* issued_per_flop, double* clamp);
+};
+// the rows (function-local constants: a namespace-scope const object of host function pointers would be emitted for the device too)
+const TrunkImpl* trunk_f32();    // net_f32.hip: exact fp32 (k_trunk_f32 / k_trunk_f32c), any width, 8x8 and 6x6
+const TrunkImpl* trunk_wino6();  // net_wino6.hip: 1-D Winograd F(2,3), 64 filters on 6x6 (BASELINE configs[4])
+const TrunkImpl* trunk_wino();   // net_wino.hip: 1-D Winograd F(2,3), 128 filters on 8x8
+const TrunkImpl* trunk_h3();     // net_h3.hip: direct 3x3, one wave per position group (32 / 64 filters, 128 on 6x6)
+const TrunkImpl* trunk_mfma();   // net_mfma.hip: direct 3x3, 128 filters on 8x8 (k_trunk16, three builds)
 
 }  // namespace oth
 
@@ -55,7 +71,11 @@ struct oth_net {
     int blocks = 0, filters = 0, board = 8;
     int precision = -1;  // OTH_PREC_*; -1 = no weights loaded
     oth::HostNet host;
-    float* d_heads = nullptr;  // one allocation: the fp32 head parameters (shared by both trunk kernels)
+    float* d_heads = nullptr;  // one allocation: the fp32 head parameters (shared by every trunk kernel)
+    // the head FCs transposed so that lanes read consecutive outputs (net_heads_wave.h, k_trunk_w's heads_block2): an
+    // allocation each, for every trunk whose Args carry them
+    float* d_pfc_wt = nullptr;   // [2*cells][cells+1]
+    float* d_vfc1_wt = nullptr;  // [cells][256]
     int* d_sat = nullptr;      // device flag: an fp16-split trunk kernel clamped an activation (oth_net_saturated)
     // Activations of the fp16-split trunks are carried PRE-SCALED by act_scale (a power of two, 16 by default: it keeps the
     // lo parts of the operand split clear of the f16 subnormals) and clamped at the f16 range of that scaled value; the
@@ -66,16 +86,8 @@ struct oth_net {
     struct ScaledBias { float* dev; std::vector<float> host; };
     std::vector<ScaledBias> scaled_bias;
     oth::HeadParams heads{};
-    // exact-fp32 MFMA path (any filter count, 8x8 and 6x6): net_f32.hip
-    oth::F32Weights* f32 = nullptr;
-    // fp16-split MFMA path (128 filters, 8x8): net_mfma.hip
-    oth::MfmaWeights* mfma = nullptr;
-    // fp16-split MFMA path, one wave per position (32 / 64 filters, 8x8 and 6x6): net_h3.hip
-    oth::H3Weights* h3 = nullptr;
-    // 1-D Winograd F(2,3) build of the 128-filter 8x8 trunk (fp16-split arithmetic): net_wino.hip
-    oth::WinoWeights* wino = nullptr;
-    // 1-D Winograd F(2,3) build of the 64-filter 6x6 trunk (BASELINE configs[4]): net_wino6.hip
-    oth::Wino6Weights* wino6 = nullptr;
+    const oth::TrunkImpl* trunk = nullptr;  // the row that serves this network at `precision`
+    void* trunk_w = nullptr;                // its packed weights (the row's own struct)
 };
 
 // The in-place MFMAs of net_mfma.hip / net_h3.hip are inline asm: hipcc inserts no wait states between a VALU write of a
@@ -92,25 +104,4 @@ struct oth_net {
 namespace oth {
 // upload host x net->act_scale to dev and keep both for oth_net_set_act_scale (dev stays owned by the caller's weight struct)
 int register_scaled_bias(oth_net* net, float* dev, std::vector<float> host);   // net.hip
-int mfma_pack_weights(oth_net* net, int precision);  // net_mfma.hip
-void mfma_free_weights(oth_net* net);
-int mfma_forward(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
-                 const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
-int h3_pack_weights(oth_net* net);  // net_h3.hip
-void h3_free_weights(oth_net* net);
-int h3_forward(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
-               const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
-int wino6_pack_weights(oth_net* net);  // net_wino6.hip
-void wino6_free_weights(oth_net* net);
-int wino6_forward(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
-                  const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
-int wino_pack_weights(oth_net* net);  // net_wino.hip
-void wino_free_weights(oth_net* net);
-int wino_positions_per_workgroup(int64_t n);   // 1 or 2: which k_trunk_w build a launch of n positions runs
-int wino_forward(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
-                 const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
-int f32_pack_weights(oth_net* net);  // net_f32.hip
-void f32_free_weights(oth_net* net);
-int f32_forward(oth_net* net, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
-                const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
 }  // namespace oth

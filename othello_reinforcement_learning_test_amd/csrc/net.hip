@@ -1,18 +1,25 @@
-// net.hip -- section 3 of include/othello_mi355x.h: evaluator object, weight loading (BatchNorm folding) and
-// dispatch to the two trunk kernels: net_f32.hip / net_f32c.hip (exact fp32 on v_mfma_f32_16x16x4_f32: every filter
-// count that is a multiple of 16 up to 256, 8x8 and 6x6; also the independent cross-check of the split kernel) and net_mfma.hip (fp16 hi/lo split on
-// v_mfma_f32_16x16x32_f16: 128 filters on 8x8, the benchmarked configuration).
+// net.hip -- section 3 of include/othello_mi355x.h: evaluator object, weight loading (BatchNorm folding), the head
+// parameters every trunk shares, and the trunk table: which kernel family runs a network is decided ONCE, in
+// oth_net_load_state, by the first row of kTrunks that serves it; forward and kernel_info call through that row.
+//   trunk_f32    net_f32.hip / net_f32c.hip  exact fp32 on v_mfma_f32_16x16x4_f32: every filter count that is a multiple
+//                                            of 16 up to 256, 8x8 and 6x6; also the cross-check of the split kernels
+//   trunk_wino6  net_wino6.hip               fp16 hi/lo split on v_mfma_f32_16x16x32_f16, 1-D Winograd: 64 filters on 6x6
+//   trunk_wino   net_wino.hip                the same for 128 filters on 8x8, the benchmarked configuration
+//   trunk_h3     net_h3.hip                  fp16 split, direct 3x3, a wave per position group: 32 / 64 filters, 128 on 6x6
+//   trunk_mfma   net_mfma.hip                fp16 split (or a single f16 pass), direct 3x3: 128 filters on 8x8
 //
 // Reference: /root/reference/src/model/net.py:139-205 (OthelloResNet.forward, eval mode).
 #include <math.h>
 #include <string.h>
 
-#include <stdlib.h>
-
-#include "net_f32.h"
+#include "net.h"
 #include "net_heads.h"
 
 namespace oth {
+
+// Priority order.  The two Winograd rows step aside under OTH_WINO6=0 / OTH_WINO=0 (read when the weights are loaded: the
+// A/B switches), which leaves their networks to the direct kernels below them.
+static const TrunkImpl* (*const kTrunks[])() = {trunk_f32, trunk_wino6, trunk_wino, trunk_h3, trunk_mfma};
 
 // ------------------------------------------------------------------------------------------------
 // state_dict blob -> folded host weights
@@ -89,17 +96,22 @@ int register_scaled_bias(oth_net* net, float* dev, std::vector<float> host) {
 
 using namespace oth;
 
+static int upload_floats(float** dev, const std::vector<float>& v) {
+    OTH_HIP(hipMalloc(dev, v.size() * sizeof(float)));
+    OTH_HIP(hipMemcpy(*dev, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+    return OTH_OK;
+}
+
 static void net_free_device(oth_net* net) {
-    net->scaled_bias.clear();   // (the device arrays belong to the weight structs freed below)
-    if (net->d_heads) (void)hipFree(net->d_heads);
-    net->d_heads = nullptr;
-    if (net->d_sat) (void)hipFree(net->d_sat);
+    net->precision = -1;
+    net->scaled_bias.clear();   // (the device arrays belong to the trunk's weight struct freed below)
+    for (void* p : {(void*)net->d_heads, (void*)net->d_pfc_wt, (void*)net->d_vfc1_wt, (void*)net->d_sat})
+        if (p) (void)hipFree(p);
+    net->d_heads = net->d_pfc_wt = net->d_vfc1_wt = nullptr;
     net->d_sat = nullptr;
-    f32_free_weights(net);
-    h3_free_weights(net);
-    mfma_free_weights(net);
-    wino_free_weights(net);
-    wino6_free_weights(net);
+    if (net->trunk) net->trunk->destroy(net->trunk_w);
+    net->trunk = nullptr;
+    net->trunk_w = nullptr;
 }
 
 extern "C" {
@@ -150,37 +162,9 @@ int oth_net_saturated(oth_net* net, int32_t* flag, void* stream) {
 int oth_net_kernel_info(const oth_net* net, int64_t n, char* name, int32_t name_cap, double* issued_per_flop,
                         double* clamp) {
     OTH_CHECK(net && net->precision >= 0, "oth_net_kernel_info: no weights loaded (call oth_net_load_state)");
-    // the same order of tests as oth_net_forward_bits below
-    const char* k;
-    double issued, cl = 0.0;
-    if (net->precision == OTH_PREC_F32) {
-        k = f32c_selected(net)
-                ? "k_trunk_f32c (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, the waves of a workgroup share a "
-                  "position group and split the output channels)"
-                : "k_trunk_f32 (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, one wave per position group)";
-        issued = 1.0;
-    } else if (net->wino6) {
-        k = "k_trunk_w6 (fused ResNet forward, 6x6, 1-D Winograd F(2,3) residual convolutions, eight positions per workgroup)";
-        issued = 3.0 * 2.0 / 3.0;   // three split products, 4 multiplies per 2 outputs instead of 6, every N-tile full
-        cl = 30000.0 / net->act_scale;   // 1875 at the default scale 16
-    } else if (net->h3) {
-        k = "k_trunk_h3 (fused ResNet forward, direct 3x3, one wave per position group)";
-        // three split products; N-tiles of 16 cells over the wave's positions (P = 2 on 6x6 with 64 filters, 4 with 32, else 1)
-        const int cells = net->board * net->board;
-        const int P = net->board == 6 ? (net->filters == 64 ? 2 : net->filters == 32 ? 4 : 1) : 1;
-        issued = 3.0 * (double)((P * cells + 15) / 16 * 16) / (double)(P * cells);
-        cl = 60000.0 / net->act_scale;   // 3750 at the default scale 16
-    } else if (net->wino) {
-        k = wino_positions_per_workgroup(n) == 2 ? "k_trunk_w<2> (fused ResNet forward, 1-D Winograd F(2,3) residual convolutions, two positions per workgroup)"
-                    : "k_trunk_w<1> (fused ResNet forward, 1-D Winograd F(2,3) residual convolutions, one position per workgroup)";
-        issued = 3.0 * 2.0 / 3.0;
-        cl = 30000.0 / net->act_scale;   // 1875 at the default scale 16
-    } else {
-        const bool x3 = net->precision != OTH_PREC_F16;
-        k = x3 ? "k_trunk16 (fused ResNet forward, direct 3x3, fp16 hi/lo split)" : "k_trunk16 (fused ResNet forward, direct 3x3, single fp16 pass)";
-        issued = (x3 ? 3.0 : 1.0) * 11.0 / 12.0;   // the all-padding row tiles of the dy = -1 / +1 taps are skipped
-        cl = 60000.0 / net->act_scale;   // 3750 at the default scale 16
-    }
+    const char* k = "";
+    double issued = 0.0, cl = 0.0;
+    net->trunk->info(net, n, &k, &issued, &cl);
     if (name && name_cap > 0) {
         strncpy(name, k, (size_t)name_cap - 1);
         name[name_cap - 1] = 0;
@@ -230,12 +214,14 @@ int oth_net_load_state(oth_net* net, const float* blob, int64_t n_floats, int pr
     OTH_CHECK(precision == OTH_PREC_F32 || precision == OTH_PREC_F16X3 || precision == OTH_PREC_F16 ||
                   precision == OTH_PREC_F16X3_DIRECT,
               "oth_net_load_state: unknown precision %d", precision);
-    // fp16-split kernels: 128 filters on 8x8 (k_trunk16: f16x3 and the single-pass f16), 32 / 64 filters on either
-    // board (k_trunk_h3: f16x3 only); everything else (16 filters and every other multiple of 16 up to 256) runs the
-    // exact-fp32 MFMA kernels
-    const bool wide = net->filters == 128 && net->board == 8;
-    const bool narrow = net->filters == 32 || net->filters == 64 || (net->filters == 128 && net->board == 6);
-    if (precision != OTH_PREC_F32 && !(wide || (narrow && precision == OTH_PREC_F16X3))) {
+    // the first row that serves the network at this precision (each row's file says what it is built for)
+    const TrunkImpl* trunk = nullptr;
+    for (auto row : kTrunks)
+        if (row()->serves(net, precision)) {
+            trunk = row();
+            break;
+        }
+    if (!trunk) {
         set_error("oth_net_load_state: no fp16-split kernel for %d filters on a %dx%d board at precision %d; use "
                   "OTH_PREC_F32 (exact fp32 MFMA)", net->filters, net->board, net->board, precision);
         return OTH_E_UNSUPPORTED;
@@ -256,28 +242,21 @@ int oth_net_load_state(oth_net* net, const float* blob, int64_t n_floats, int pr
     const size_t o_v2w = push(h.vfc2_w), o_v2b = push(h.vfc2_b);
     OTH_HIP(hipMalloc(&net->d_sat, sizeof(int)));
     OTH_HIP(hipMemset(net->d_sat, 0, sizeof(int)));
-    OTH_HIP(hipMalloc(&net->d_heads, flat.size() * sizeof(float)));
-    OTH_HIP(hipMemcpy(net->d_heads, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = upload_floats(&net->d_heads, flat)) return rc;
     const float* d = net->d_heads;
     net->heads = HeadParams{d + o_pw, d + o_pb, d + o_vw, d + o_vb, d + o_pfw, d + o_pfb, d + o_v1w, d + o_v1b, d + o_v2w, d + o_v2b};
-    int r = precision == OTH_PREC_F32 ? f32_pack_weights(net)
-                                      : (wide ? mfma_pack_weights(net, precision) : h3_pack_weights(net));
-    if (r != OTH_OK) return r;
-    // A 128-filter 8x8 network in f16x3 runs the 1-D Winograd F(2,3) trunk (net_wino.hip: 1.375x fewer MFMAs, +9 % games/s
-    // on the bench; its one-position build serves the launches of <= 256 positions, so a position's outputs do not depend
-    // on the launch size); OTH_WINO=0 keeps the direct kernel (k_trunk16) -- the A/B switch.
-    const char* wino_env = getenv("OTH_WINO");
-    if (precision == OTH_PREC_F16X3 && wide && net->board == 8 && !(wino_env && atoi(wino_env) == 0)) {
-        r = wino_pack_weights(net);
-        if (r != OTH_OK) return r;
-    }
-    // A 64-filter 6x6 network (BASELINE configs[4]) in f16x3 runs the 6x6 Winograd trunk (net_wino6.hip: eight positions per
-    // workgroup, 1.5x fewer MFMAs and no padded cells); OTH_WINO6=0 keeps k_trunk_h3 -- the A/B switch.
-    const char* wino6_env = getenv("OTH_WINO6");
-    if (precision == OTH_PREC_F16X3 && net->filters == 64 && net->board == 6 && !(wino6_env && atoi(wino6_env) == 0)) {
-        r = wino6_pack_weights(net);
-        if (r != OTH_OK) return r;
-    }
+    // ---- the two head FCs transposed: [input][output], so that the lanes of a wave read consecutive outputs
+    const int cells = net->board * net->board, NP = cells + 1;
+    std::vector<float> pt((size_t)2 * cells * NP), vt((size_t)cells * 256);
+    for (int o = 0; o < NP; ++o)
+        for (int i = 0; i < 2 * cells; ++i) pt[(size_t)i * NP + o] = h.pfc_w[(size_t)o * 2 * cells + i];
+    for (int o = 0; o < 256; ++o)
+        for (int i = 0; i < cells; ++i) vt[(size_t)i * 256 + o] = h.vfc1_w[(size_t)o * cells + i];
+    if (int rc = upload_floats(&net->d_pfc_wt, pt)) return rc;
+    if (int rc = upload_floats(&net->d_vfc1_wt, vt)) return rc;
+    // ---- the trunk's weights: the selected row's only
+    net->trunk = trunk;
+    if (int rc = trunk->pack(net)) return rc;
     net->precision = precision;
     return OTH_OK;
 }
@@ -289,11 +268,7 @@ int oth_net_forward_bits(oth_net* net, const uint64_t* sb, const uint64_t* ob, c
     OTH_CHECK(n >= 0 && (n == 0 || (sb && ob && lg && logp && v)), "oth_net_forward: null pointer or negative n");
     if (n == 0) return OTH_OK;
     OTH_BIND(net->device);
-    if (net->precision == OTH_PREC_F32) return f32_forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
-    if (net->wino6) return wino6_forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
-    if (net->h3) return h3_forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
-    if (net->wino) return wino_forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
-    return mfma_forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
+    return net->trunk->forward(net, sb, ob, lg, n, n_valid, logp, v, as_stream(stream));
 }
 
 int oth_net_forward_planes(oth_net* net, const float* x, int64_t n, float* logp, float* v, void* stream) {

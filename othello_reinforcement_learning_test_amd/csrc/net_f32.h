@@ -4,20 +4,18 @@
 #pragma once
 #include <vector>
 
-#include "net.h"
+#include "net_pack.h"
 
 namespace oth {
 
 using f32x4 = float __attribute__((ext_vector_type(4)));
 
 struct F32Weights {
-    float4* d_w = nullptr;       // [layer][k-step][chunk][64 lanes] x 16 B (k_trunk_f32; null where only k_trunk_f32c runs)
-    float4* d_wc = nullptr;      // [layer][wave][k-step][chunk][64 lanes] x 16 B (k_trunk_f32c; null where it has no build)
-    float* d_bias = nullptr;     // [layers][F]
-    float* d_pfc_wt = nullptr;   // [2*cells][cells+1] (transposed policy FC)
-    float* d_vfc1_wt = nullptr;  // [cells][256]      (transposed value FC1)
-    std::vector<uint32_t> layer_off;    // in float4 units, into d_w
-    std::vector<uint32_t> layer_off_c;  // in float4 units, into d_wc
+    DevBuf<float4> w;      // [layer][k-step][chunk][64 lanes] x 16 B (k_trunk_f32; null where only k_trunk_f32c runs)
+    DevBuf<float4> wc;     // [layer][wave][k-step][chunk][64 lanes] x 16 B (k_trunk_f32c; null where it has no build)
+    DevBuf<float> bias;    // [layers][F]
+    std::vector<uint32_t> layer_off;    // in float4 units, into w
+    std::vector<uint32_t> layer_off_c;  // in float4 units, into wc
 };
 
 struct F32Args {
@@ -57,9 +55,9 @@ int f32c_waves(int filters);
 // true when a launch on `net` runs k_trunk_f32c: the widths only it serves, or OTH_F32_COOP=1 (read per call: the A/B
 // switch) where both kernels have a build
 bool f32c_selected(const oth_net* net);
-// append the fragment-ordered weights of k_trunk_f32c to fw (called by f32_pack_weights with fw->d_bias etc. still unset)
+// the fragment-ordered weights of k_trunk_f32c -> fw->wc (called by f32_pack)
 int f32c_pack_weights(oth_net* net, F32Weights* fw);
-int f32c_forward(oth_net* net, F32Args& a, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
+int f32c_forward(oth_net* net, const F32Weights* fw, F32Args& a, const uint64_t* self_b, const uint64_t* opp_b, const uint64_t* legal, int64_t n,
                  const int32_t* n_valid, float* logp, float* v, hipStream_t stream);
 
 }  // namespace oth

@@ -173,17 +173,6 @@ __global__ __launch_bounds__(64 * WPB) void k_trunk_f32(F32Args a, const uint64_
 // ------------------------------------------------------------------------------------------------
 // host: pack weights into fragment order
 // ------------------------------------------------------------------------------------------------
-void f32_free_weights(oth_net* net) {
-    if (!net->f32) return;
-    if (net->f32->d_w) (void)hipFree(net->f32->d_w);
-    if (net->f32->d_wc) (void)hipFree(net->f32->d_wc);
-    if (net->f32->d_bias) (void)hipFree(net->f32->d_bias);
-    if (net->f32->d_pfc_wt) (void)hipFree(net->f32->d_pfc_wt);
-    if (net->f32->d_vfc1_wt) (void)hipFree(net->f32->d_vfc1_wt);
-    delete net->f32;
-    net->f32 = nullptr;
-}
-
 // FoldedConv weights are [tap][cin][cout]; lane l of k-step kc needs, for e = tap*NB + blk,
 // W[cout = 16*blk + (l & 15)][cin = 4*kc + (l >> 4)][tap]  (cin >= c.cin: zero -- the stem's fourth plane)
 static void pack_layer(const FoldedConv& c, int F, int kc_steps, std::vector<float>& out) {
@@ -200,12 +189,16 @@ static void pack_layer(const FoldedConv& c, int F, int kc_steps, std::vector<flo
             }
 }
 
-int f32_pack_weights(oth_net* net) {
+static bool f32_serves(const oth_net*, int precision) { return precision == OTH_PREC_F32; }
+
+static void f32_destroy(void* w) { delete static_cast<F32Weights*>(w); }
+
+static int f32_pack(oth_net* net) {
     const HostNet& hn = net->host;
-    const int F = hn.filters, L = 1 + 2 * hn.blocks, cells = net->board * net->board, NP = cells + 1;
+    const int F = hn.filters, L = 1 + 2 * hn.blocks;
     OTH_CHECK(L <= kMaxTrunkLayers, "too many layers");
     F32Weights* fw = new F32Weights();
-    net->f32 = fw;
+    net->trunk_w = fw;
     std::vector<float> w, bias((size_t)L * F);
     fw->layer_off.resize(L);
     const bool one_wave = F <= 128;   // k_trunk_f32 has a build; wider networks run k_trunk_f32c alone
@@ -215,24 +208,11 @@ int f32_pack_weights(oth_net* net) {
         if (one_wave) pack_layer(c, F, l == 0 ? 1 : F / 4, w);
         for (int i = 0; i < F; ++i) bias[(size_t)l * F + i] = c.bias[i];
     }
-    if (f32c_waves(F)) {
-        const int r = f32c_pack_weights(net, fw);
-        if (r != OTH_OK) return r;
-    }
-    std::vector<float> pt((size_t)2 * cells * NP), vt((size_t)cells * 256);
-    for (int o = 0; o < NP; ++o)
-        for (int i = 0; i < 2 * cells; ++i) pt[(size_t)i * NP + o] = hn.pfc_w[(size_t)o * 2 * cells + i];
-    for (int o = 0; o < 256; ++o)
-        for (int i = 0; i < cells; ++i) vt[(size_t)i * 256 + o] = hn.vfc1_w[(size_t)o * cells + i];
-    if (one_wave) OTH_HIP(hipMalloc(&fw->d_w, w.size() * 4));
-    OTH_HIP(hipMalloc(&fw->d_bias, bias.size() * 4));
-    OTH_HIP(hipMalloc(&fw->d_pfc_wt, pt.size() * 4));
-    OTH_HIP(hipMalloc(&fw->d_vfc1_wt, vt.size() * 4));
-    if (one_wave) OTH_HIP(hipMemcpy(fw->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(fw->d_bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(fw->d_pfc_wt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(fw->d_vfc1_wt, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    if (f32c_waves(F))
+        if (int rc = f32c_pack_weights(net, fw)) return rc;
+    if (one_wave)
+        if (int rc = fw->w.upload(w)) return rc;
+    return fw->bias.upload(bias);
 }
 
 template <int F, int BS, int P, int WPB>
@@ -241,13 +221,7 @@ static int launch_f32(oth_net* net, const F32Args& a, const uint64_t* sb, const 
     using G = TrunkGeom<F, BS, P>;
     constexpr size_t lds = (size_t)WPB * G::WAVE_WORDS * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool attr_set_dev[64] = {};  // per device: the attribute belongs to the (function, device) pair
-    bool& attr_set = attr_set_dev[net->device & 63];
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_f32<F, BS, P, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_f32<F, BS, P, WPB>, net->device, (int)lds)) return rc;
     const int64_t per_block = (int64_t)P * WPB;
     const unsigned grid = (unsigned)((n + per_block - 1) / per_block);
     hipLaunchKernelGGL((k_trunk_f32<F, BS, P, WPB>), dim3(grid), dim3(64 * WPB), lds, stream, a, sb, ob, lg, n, n_valid,
@@ -256,20 +230,20 @@ static int launch_f32(oth_net* net, const F32Args& a, const uint64_t* sb, const 
     return OTH_OK;
 }
 
-int f32_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-                const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->f32, "fp32 MFMA weights not packed");
+static int f32_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                       const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    const F32Weights* fw = static_cast<const F32Weights*>(net->trunk_w);
     F32Args a;
     memset(&a, 0, sizeof(a));
-    a.w = net->f32->d_w;
-    a.bias = net->f32->d_bias;
+    a.w = fw->w.get();
+    a.bias = fw->bias.get();
     a.n_layers = 1 + 2 * net->blocks;
-    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = net->f32->layer_off[l];
+    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = fw->layer_off[l];
     a.heads = net->heads;
-    a.pfc_wt = net->f32->d_pfc_wt;
-    a.vfc1_wt = net->f32->d_vfc1_wt;
+    a.pfc_wt = net->d_pfc_wt;
+    a.vfc1_wt = net->d_vfc1_wt;
     const int F = net->filters;
-    if (f32c_selected(net)) return f32c_forward(net, a, sb, ob, lg, n, n_valid, logp, v, stream);
+    if (f32c_selected(net)) return f32c_forward(net, fw, a, sb, ob, lg, n, n_valid, logp, v, stream);
 #define OTH_F32_CASE(FF, BB, PP, WW) \
     if (F == FF && net->board == BB) return launch_f32<FF, BB, PP, WW>(net, a, sb, ob, lg, n, n_valid, logp, v, stream)
     // positions per wave / waves per workgroup chosen for LDS (F planes of P positions per wave) and registers
@@ -295,10 +269,23 @@ int f32_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint
     return OTH_E_UNSUPPORTED;
 }
 
+static void f32_info(const oth_net* net, int64_t, const char** name, double* issued_per_flop, double* clamp) {
+    *name = f32c_selected(net)
+                ? "k_trunk_f32c (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, the waves of a workgroup share a "
+                  "position group and split the output channels)"
+                : "k_trunk_f32 (fused ResNet forward, exact fp32 on v_mfma_f32_16x16x4_f32, one wave per position group)";
+    *issued_per_flop = 1.0;
+    *clamp = 0.0;   // fp32 activations: nothing to clamp
+}
+
+const TrunkImpl* trunk_f32() {
+    static const TrunkImpl row = {f32_serves, f32_pack, f32_destroy, f32_forward, f32_info};
+    return &row;
+}
+
 }  // namespace oth
 
 // The cooperative kernel is compiled as part of this translation unit.  csrc/Makefile is one of the files whose hash
 // dates the committed PMC traffic figure of the benchmarked trunk (bench.py TRUNK_SOURCES): a new entry in SRCS would
-// make that figure read as stale although no byte of the kernel it was measured on has changed.  (The Makefile's
-// dependency list does not name net_f32.h / net_f32c.hip: after editing them, touch this file.)
+// make that figure read as stale although no byte of the kernel it was measured on has changed.
 #include "net_f32c.hip"

@@ -210,9 +210,7 @@ int f32c_pack_weights(oth_net* net, F32Weights* fw) {
         fw->layer_off_c[l] = (uint32_t)(w.size() / 4);
         pack_layer_c(l == 0 ? hn.stem : hn.res[l - 1], F, W, l == 0 ? 1 : F / 4, w);
     }
-    OTH_HIP(hipMalloc(&fw->d_wc, w.size() * 4));
-    OTH_HIP(hipMemcpy(fw->d_wc, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    return fw->wc.upload(w);
 }
 
 template <int F, int BS, int P, int W>
@@ -221,13 +219,7 @@ static int launch_f32c(oth_net* net, const F32Args& a, const uint64_t* sb, const
     using G = TrunkGeom<F, BS, P>;
     constexpr size_t lds = (size_t)G::WAVE_WORDS * sizeof(float);   // the planes of one position group + its head scratch
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool attr_set_dev[64] = {};  // per device: the attribute belongs to the (function, device) pair
-    bool& attr_set = attr_set_dev[net->device & 63];
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_f32c<F, BS, P, W>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_f32c<F, BS, P, W>, net->device, (int)lds)) return rc;
     const unsigned grid = (unsigned)((n + P - 1) / P);
     hipLaunchKernelGGL((k_trunk_f32c<F, BS, P, W>), dim3(grid), dim3(64 * W), lds, stream, a, sb, ob, lg, n, n_valid, logp,
                        v);
@@ -235,11 +227,11 @@ static int launch_f32c(oth_net* net, const F32Args& a, const uint64_t* sb, const
     return OTH_OK;
 }
 
-int f32c_forward(oth_net* net, F32Args& a, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-                 const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->f32 && net->f32->d_wc, "fp32 cooperative trunk: weights not packed");
-    a.w = net->f32->d_wc;
-    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = net->f32->layer_off_c[l];
+int f32c_forward(oth_net* net, const F32Weights* fw, F32Args& a, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg,
+                 int64_t n, const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    OTH_CHECK(fw->wc.get(), "fp32 cooperative trunk: weights not packed");
+    a.w = fw->wc.get();
+    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = fw->layer_off_c[l];
     const int F = net->filters;
     // positions per workgroup: one on 8x8 (4 tiles of 16 cells), two on 6x6 (72 cells in 5 tiles); waves: f32c_waves
 #define OTH_F32C_CASE(FF, WW)                                                                                         \

@@ -28,9 +28,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "net.h"
+#include "net_pack.h"
 #include "net_heads_wave.h"
 #include "net_epilogue.h"
+#include "net_stamps.h"
 
 namespace oth {
 
@@ -40,13 +41,25 @@ using f32x4 = float __attribute__((ext_vector_type(4)));
 
 
 struct H3Weights {
-    uint4* d_w = nullptr;        // [layer][tap][k-step][row block][hi, lo][64 lanes] x 16 B
-    float* d_bias = nullptr;     // [layers][F], x act_scale (register_scaled_bias)
-    float* d_inv = nullptr;      // [layers] 1 / weight scale
-    float* d_pfc_wt = nullptr;   // transposed head FCs (net_heads_wave.h)
-    float* d_vfc1_wt = nullptr;
+    DevBuf<uint4> w;        // [layer][tap][k-step][row block][hi, lo][64 lanes] x 16 B
+    DevBuf<float> bias;     // [layers][F], x act_scale (register_scaled_bias)
+    DevBuf<float> inv;      // [layers] 1 / weight scale
     std::vector<uint32_t> layer_off;  // in uint4 units
 };
+
+// The builds: positions per wave and waves per workgroup of every (filters, board) the kernel serves.  h3_forward
+// instantiates them in this order; h3_serves and h3_info read the same rows.
+struct H3Build { int filters, board, P, wpb; };
+constexpr H3Build kH3Builds[] = {
+    {64, 8, 1, 4}, {32, 8, 1, 4}, {64, 6, 2, 4}, {32, 6, 4, 4},
+    {128, 6, 1, 4},   // 128 filters on 6x6 (8x8 has k_trunk16)
+};
+constexpr int kH3NumBuilds = sizeof(kH3Builds) / sizeof(kH3Builds[0]);
+static const H3Build* h3_build_of(const oth_net* net) {
+    for (const H3Build& b : kH3Builds)
+        if (b.filters == net->filters && b.board == net->board) return &b;
+    return nullptr;
+}
 
 struct H3Args {
     const uint4* w;
@@ -99,22 +112,8 @@ __device__ __forceinline__ f32x4 mfma_h(half8 a, half8 b, f32x4 c) {
     }
 }
 
-#ifdef OTH_STAMPS
-__device__ __forceinline__ unsigned long long h3_clk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-__device__ __forceinline__ unsigned long long h3_realclk() {   // 100 MHz constant clock
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define OTH_HSTAMP(i) { const unsigned long long t1_ = h3_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
+#ifdef OTH_STAMPS   // net_stamps.h
+#define OTH_HSTAMP(i) { const unsigned long long t1_ = oth_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
 #else
 #define OTH_HSTAMP(i)
 #endif
@@ -139,8 +138,8 @@ __global__ __launch_bounds__(64 * WPB) void k_trunk_h3(H3Args a, const uint64_t*
         nv = k < n ? k : n;
     }
 #ifdef OTH_STAMPS
-    unsigned long long ph_[5] = {0, 0, 0, 0, 0}, t0_ = h3_clk();   // prologue | weight wait + conv | epilogue | planes | heads
-    const unsigned long long tstart_ = t0_, rstart_ = h3_realclk();
+    unsigned long long ph_[5] = {0, 0, 0, 0, 0}, t0_ = oth_clk();   // prologue | weight wait + conv | epilogue | planes | heads
+    const unsigned long long tstart_ = t0_, rstart_ = oth_realclk();
 #endif
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t pos0 = ((int64_t)blockIdx.x * WPB + wave) * P;
@@ -358,8 +357,8 @@ __global__ __launch_bounds__(64 * WPB) void k_trunk_h3(H3Args a, const uint64_t*
     if (a.dbg && lane == 0) {
         unsigned long long* o = a.dbg + ((size_t)blockIdx.x * WPB + wave) * 8;
         for (int i = 0; i < 5; ++i) o[i] = ph_[i];
-        o[5] = h3_clk() - tstart_;
-        o[6] = h3_realclk() - rstart_;
+        o[5] = oth_clk() - tstart_;
+        o[6] = oth_realclk() - rstart_;
     }
 #endif
 }
@@ -367,36 +366,11 @@ __global__ __launch_bounds__(64 * WPB) void k_trunk_h3(H3Args a, const uint64_t*
 // ------------------------------------------------------------------------------------------------
 // host: pack weights into A-fragment order
 // ------------------------------------------------------------------------------------------------
-void h3_free_weights(oth_net* net) {
-    if (!net->h3) return;
-    H3Weights* w = net->h3;
-    if (w->d_w) (void)hipFree(w->d_w);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_inv) (void)hipFree(w->d_inv);
-    if (w->d_pfc_wt) (void)hipFree(w->d_pfc_wt);
-    if (w->d_vfc1_wt) (void)hipFree(w->d_vfc1_wt);
-    delete w;
-    net->h3 = nullptr;
-}
-
-static inline void split_h3(float v, uint16_t& hi, uint16_t& lo) {
-    const _Float16 hh = (_Float16)v;
-    const _Float16 ll = (_Float16)(v - (float)hh);
-    memcpy(&hi, &hh, 2);
-    memcpy(&lo, &ll, 2);
-}
-
 // A fragment of v_mfma_f32_16x16x32_f16: lane l holds W[row = l&15][k = 8*(l>>4) + j], j = 0..7.
 // FoldedConv weights are [tap][cin][cout]; cin >= c.cin is zero (the stem's 3 planes in a 32-wide k-step).
 static float pack_layer_h3(const FoldedConv& c, int F, int kk_steps, std::vector<uint16_t>& out) {
     const int NB = F / 16;
-    float mx = 0.f;
-    for (float x : c.w) mx = fmaxf(mx, fabsf(x));
-    int e = 0;
-    if (mx > 0.f) e = (int)floorf(log2f(16384.0f / mx));  // largest |w| lands in [8192, 16384]
-    if (e > 24) e = 24;
-    if (e < -24) e = -24;
-    const float scale = ldexpf(1.0f, e);
+    const float scale = pow2_weight_scale(max_abs(c.w));
     const size_t base = out.size();
     out.resize(base + (size_t)9 * kk_steps * NB * 2 * 64 * 8, 0);
     for (int kk = 0; kk < kk_steps; ++kk)
@@ -407,7 +381,7 @@ static float pack_layer_h3(const FoldedConv& c, int F, int kk_steps, std::vector
                         const int co = 16 * b + (l & 15), ci = 32 * kk + 8 * (l >> 4) + j;
                         const float v = ci < c.cin ? c.w[((size_t)tap * c.cin + ci) * c.cout + co] * scale : 0.f;
                         uint16_t hi, lo;
-                        split_h3(v, hi, lo);
+                        split_f16(v, hi, lo);
                         const size_t step = (size_t)kk * 9 + tap;
                         const size_t frag = base + ((step * NB + b) * 2) * 64 * 8;
                         out[frag + (size_t)l * 8 + j] = hi;
@@ -416,14 +390,19 @@ static float pack_layer_h3(const FoldedConv& c, int F, int kk_steps, std::vector
     return scale;
 }
 
-int h3_pack_weights(oth_net* net) {
+static bool h3_serves(const oth_net* net, int precision) {
+    return precision == OTH_PREC_F16X3 && h3_build_of(net);
+}
+
+static void h3_destroy(void* w) { delete static_cast<H3Weights*>(w); }
+
+static int h3_pack(oth_net* net) {
     const HostNet& hn = net->host;
-    const int F = hn.filters, L = 1 + 2 * hn.blocks, cells = net->board * net->board, NP = cells + 1;
-    OTH_CHECK(F == 32 || F == 64 || (F == 128 && net->board == 6),
-              "the wave-per-position fp16-split trunk is built for 32 and 64 filters (and 128 on 6x6)");
+    const int F = hn.filters, L = 1 + 2 * hn.blocks;
+    OTH_CHECK(h3_build_of(net), "the wave-per-position fp16-split trunk is built for 32 and 64 filters (and 128 on 6x6)");
     OTH_CHECK(L <= kMaxTrunkLayers, "too many layers");
     H3Weights* hw = new H3Weights();
-    net->h3 = hw;
+    net->trunk_w = hw;
     std::vector<uint16_t> w;
     std::vector<float> bias((size_t)L * F), inv(L);
     hw->layer_off.resize(L);
@@ -434,22 +413,10 @@ int h3_pack_weights(oth_net* net) {
         inv[l] = 1.0f / sc;   // accumulator = (16 x) * (sc w): times 1/sc gives 16 * y
         for (int i = 0; i < F; ++i) bias[(size_t)l * F + i] = c.bias[i];
     }
-    std::vector<float> pt((size_t)2 * cells * NP), vt((size_t)cells * 256);
-    for (int o = 0; o < NP; ++o)
-        for (int i = 0; i < 2 * cells; ++i) pt[(size_t)i * NP + o] = hn.pfc_w[(size_t)o * 2 * cells + i];
-    for (int o = 0; o < 256; ++o)
-        for (int i = 0; i < cells; ++i) vt[(size_t)i * 256 + o] = hn.vfc1_w[(size_t)o * cells + i];
-    OTH_HIP(hipMalloc(&hw->d_w, w.size() * 2));
-    OTH_HIP(hipMalloc(&hw->d_bias, bias.size() * 4));
-    OTH_HIP(hipMalloc(&hw->d_inv, inv.size() * 4));
-    OTH_HIP(hipMalloc(&hw->d_pfc_wt, pt.size() * 4));
-    OTH_HIP(hipMalloc(&hw->d_vfc1_wt, vt.size() * 4));
-    OTH_HIP(hipMemcpy(hw->d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-    if (int rc = register_scaled_bias(net, hw->d_bias, std::move(bias))) return rc;
-    OTH_HIP(hipMemcpy(hw->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(hw->d_pfc_wt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(hw->d_vfc1_wt, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    if (int rc = hw->w.upload(w)) return rc;
+    if (int rc = hw->bias.alloc(bias.size() * sizeof(float))) return rc;
+    if (int rc = register_scaled_bias(net, hw->bias.get(), std::move(bias))) return rc;
+    return hw->inv.upload(inv);
 }
 
 template <int F, int BS, int P, int WPB>
@@ -458,13 +425,7 @@ static int launch_h3(oth_net* net, const H3Args& a, const uint64_t* sb, const ui
     using G = H3Geom<F, BS, P>;
     constexpr size_t lds = (size_t)WPB * G::WAVE_BYTES;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool attr_set_dev[64] = {};  // per device: the attribute belongs to the (function, device) pair
-    bool& attr_set = attr_set_dev[net->device & 63];
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_h3<F, BS, P, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_h3<F, BS, P, WPB>, net->device, (int)lds)) return rc;
     const int64_t per_block = (int64_t)P * WPB;
     const unsigned grid = (unsigned)((n + per_block - 1) / per_block);
 #ifdef OTH_STAMPS
@@ -496,32 +457,50 @@ static int launch_h3(oth_net* net, const H3Args& a, const uint64_t* sb, const ui
     return OTH_OK;
 }
 
-int h3_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-               const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->h3, "fp16-split weights not packed");
+// the launch of build I of kH3Builds, or of the first later one that matches the network
+template <int I = 0>
+static int h3_dispatch(oth_net* net, const H3Args& a, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                       const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    if constexpr (I < kH3NumBuilds) {
+        constexpr H3Build b = kH3Builds[I];
+        if (net->filters == b.filters && net->board == b.board)
+            return launch_h3<b.filters, b.board, b.P, b.wpb>(net, a, sb, ob, lg, n, n_valid, logp, v, stream);
+        return h3_dispatch<I + 1>(net, a, sb, ob, lg, n, n_valid, logp, v, stream);
+    } else {
+        set_error("fp16-split wave trunk: unsupported filters %d / board %d", net->filters, net->board);
+        return OTH_E_UNSUPPORTED;
+    }
+}
+
+static int h3_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                      const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    const H3Weights* hw = static_cast<const H3Weights*>(net->trunk_w);
     H3Args a;
     memset(&a, 0, sizeof(a));
-    a.w = net->h3->d_w;
-    a.bias = net->h3->d_bias;
-    a.inv = net->h3->d_inv;
+    a.w = hw->w.get();
+    a.bias = hw->bias.get();
+    a.inv = hw->inv.get();
     a.n_layers = 1 + 2 * net->blocks;
-    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = net->h3->layer_off[l];
+    for (int l = 0; l < a.n_layers; ++l) a.layer_off[l] = hw->layer_off[l];
     a.heads = net->heads;
-    a.pfc_wt = net->h3->d_pfc_wt;
-    a.vfc1_wt = net->h3->d_vfc1_wt;
+    a.pfc_wt = net->d_pfc_wt;
+    a.vfc1_wt = net->d_vfc1_wt;
     a.sat = net->d_sat;
     a.act_scale = net->act_scale;
-    const int F = net->filters;
-#define OTH_H3_CASE(FF, BB, PP, WW) \
-    if (F == FF && net->board == BB) return launch_h3<FF, BB, PP, WW>(net, a, sb, ob, lg, n, n_valid, logp, v, stream)
-    OTH_H3_CASE(64, 8, 1, 4);
-    OTH_H3_CASE(32, 8, 1, 4);
-    OTH_H3_CASE(64, 6, 2, 4);
-    OTH_H3_CASE(32, 6, 4, 4);
-    OTH_H3_CASE(128, 6, 1, 4);   // 128 filters on 6x6 (8x8 has k_trunk16)
-#undef OTH_H3_CASE
-    set_error("fp16-split wave trunk: unsupported filters %d / board %d", F, net->board);
-    return OTH_E_UNSUPPORTED;
+    return h3_dispatch(net, a, sb, ob, lg, n, n_valid, logp, v, stream);
+}
+
+static void h3_info(const oth_net* net, int64_t, const char** name, double* issued_per_flop, double* clamp) {
+    *name = "k_trunk_h3 (fused ResNet forward, direct 3x3, one wave per position group)";
+    // three split products; N-tiles of 16 cells over the P positions of a wave
+    const int cells = net->board * net->board, P = h3_build_of(net)->P;
+    *issued_per_flop = 3.0 * (double)((P * cells + 15) / 16 * 16) / (double)(P * cells);
+    *clamp = 60000.0 / net->act_scale;   // 3750 at the default scale 16
+}
+
+const TrunkImpl* trunk_h3() {
+    static const TrunkImpl row = {h3_serves, h3_pack, h3_destroy, h3_forward, h3_info};
+    return &row;
 }
 
 }  // namespace oth

@@ -34,8 +34,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "net.h"
+#include "net_pack.h"
 #include "net_heads.h"
+#include "net_stamps.h"
 
 namespace oth {
 
@@ -51,11 +52,10 @@ constexpr float kActClamp = 60000.0f;          // activations x act_scale are cl
                                                // <= 60000 / act_scale (3750 at the default scale 16; oth_net::act_scale)
 
 struct MfmaWeights {
-    int blocks = 0;
-    uint4* d_w = nullptr;      // fragments: [layer][step 0..71][wave 0..3][plane hi,lo][64 lanes] x 16 B
-    uint4* d_stem = nullptr;   // [step 0..1][wave][plane][64 lanes]
-    float* d_bias = nullptr;   // [1 + 2*blocks][128], x act_scale (register_scaled_bias)
-    float* d_inv = nullptr;    // [1 + 2*blocks] 1 / weight_scale
+    DevBuf<uint4> w;      // fragments: [layer][step 0..35][wave 0..3][rb0 hi, rb0 lo, rb1 hi, rb1 lo][64 lanes] x 16 B
+    DevBuf<uint4> stem;   // [wave][rb0 hi, rb0 lo, rb1 hi, rb1 lo][64 lanes] (pack_stem_f16 over the 8 row blocks)
+    DevBuf<float> bias;   // [1 + 2*blocks][128], x act_scale (register_scaled_bias)
+    DevBuf<float> inv;    // [1 + 2*blocks] 1 / weight_scale
 };
 
 struct MfmaArgs {
@@ -71,22 +71,7 @@ struct MfmaArgs {
     float act_scale;          // oth_net::act_scale: the stem's input value and the heads' un-scaling
 };
 
-#ifdef OTH_STAMPS
-// Diagnostic build: s_memtime phase stamps (never compiled into the shipped library).
-__device__ __forceinline__ unsigned long long oth_clk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-__device__ __forceinline__ unsigned long long oth_realclk() {   // 100 MHz constant clock
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
+#ifdef OTH_STAMPS   // diagnostic build: s_memtime phase stamps (net_stamps.h)
 #define OTH_STAMP(i) { const unsigned long long t1_ = oth_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
 #else
 #define OTH_STAMP(i)
@@ -518,32 +503,17 @@ __global__ __launch_bounds__(256, (TP == 2 ? 2 : 1)) void k_trunk16(MfmaArgs a, 
 // ------------------------------------------------------------------------------------------------
 // host: pack weights into fragment order
 // ------------------------------------------------------------------------------------------------
-static inline void split_f16(float v, uint16_t& hi, uint16_t& lo) {
-    const _Float16 hh = (_Float16)v;
-    const _Float16 ll = (_Float16)(v - (float)hh);
-    memcpy(&hi, &hh, 2);
-    memcpy(&lo, &ll, 2);
-}
-
-// A fragment of v_mfma_f32_16x16x32_f16: lane l holds W[row = l&15][k = 8*(l>>4) + j].  Stream per layer:
-// [step (32 channels)][wave][rb0 hi, rb0 lo, rb1 hi, rb1 lo][64 lanes] x 16 B.
-static float pack_conv16(const FoldedConv& c, std::vector<uint16_t>& out, size_t base, int steps,
-                         const std::vector<int>& k_map) {
-    float mx = 0.f;
-    for (float x : c.w) mx = fmaxf(mx, fabsf(x));
-    int e = 0;
-    if (mx > 0.f) e = (int)floorf(log2f(16384.0f / mx));
-    if (e > 24) e = 24;
-    if (e < -24) e = -24;
-    const float scale = ldexpf(1.0f, e);
-    for (int s = 0; s < steps; ++s)
+// A fragment of v_mfma_f32_16x16x32_f16: lane l holds W[row = l&15][k = 8*(l>>4) + j], gemm k = tap*128 + ci.  Stream per
+// layer: [step (32 channels)][wave][rb0 hi, rb0 lo, rb1 hi, rb1 lo][64 lanes] x 16 B.
+static float pack_conv16(const FoldedConv& c, std::vector<uint16_t>& out, size_t base) {
+    const float scale = pow2_weight_scale(max_abs(c.w));
+    for (int s = 0; s < 36; ++s)
         for (int w = 0; w < 4; ++w)
             for (int rb = 0; rb < 2; ++rb)
                 for (int l = 0; l < 64; ++l)
                     for (int j = 0; j < 8; ++j) {
                         const int k = s * 32 + 8 * (l >> 4) + j, col = w * 32 + rb * 16 + (l & 15);
-                        const int src = k_map[k];
-                        const float v = src < 0 ? 0.f : c.w[(size_t)src * c.cout + col] * scale;
+                        const float v = c.w[(size_t)k * c.cout + col] * scale;
                         uint16_t hi, lo;
                         split_f16(v, hi, lo);
                         const size_t frag = base + ((size_t)(s * 4 + w) * 4 + rb * 2) * 64 * 8;  // in halfs
@@ -553,62 +523,43 @@ static float pack_conv16(const FoldedConv& c, std::vector<uint16_t>& out, size_t
     return scale;
 }
 
-void mfma_free_weights(oth_net* net) {
-    if (!net->mfma) return;
-    if (net->mfma->d_w) (void)hipFree(net->mfma->d_w);
-    if (net->mfma->d_stem) (void)hipFree(net->mfma->d_stem);
-    if (net->mfma->d_bias) (void)hipFree(net->mfma->d_bias);
-    if (net->mfma->d_inv) (void)hipFree(net->mfma->d_inv);
-    delete net->mfma;
-    net->mfma = nullptr;
+static bool mfma_serves(const oth_net* net, int precision) {   // f16x3, f16x3_direct and the single-pass f16
+    return precision != OTH_PREC_F32 && net->filters == 128 && net->board == 8;
 }
 
-int mfma_pack_weights(oth_net* net, int precision) {
-    (void)precision;
+static void mfma_destroy(void* w) { delete static_cast<MfmaWeights*>(w); }
+
+static int mfma_pack(oth_net* net) {
     const HostNet& hn = net->host;
     OTH_CHECK(hn.filters == 128, "MFMA trunk needs 128 filters");
     const int L = 2 * hn.blocks;
     MfmaWeights* mw = new MfmaWeights();
-    mw->blocks = hn.blocks;
-    net->mfma = mw;
-    const size_t frag_halfs = 2 * 64 * 8;                 // hi + lo, per (step, wave)
-    const size_t layer_halfs = (size_t)72 * 4 * frag_halfs;
-    std::vector<uint16_t> w((size_t)L * layer_halfs), stem((size_t)2 * 4 * frag_halfs);
+    net->trunk_w = mw;
+    const size_t layer_halfs = (size_t)36 * 4 * 4 * 64 * 8;   // (step, wave) x [rb0 hi, rb0 lo, rb1 hi, rb1 lo]
+    std::vector<uint16_t> w((size_t)L * layer_halfs), stem;
     std::vector<float> bias((size_t)(L + 1) * 128), inv(L + 1);
-    std::vector<int> km(1152);
-    for (int k = 0; k < 1152; ++k) km[k] = k;  // k = tap*128 + ci, steps ordered (tap, kk)
-    std::vector<int> ks(32, -1);               // stem: gemm k = tap*3 + plane for k < 27
-    for (int k = 0; k < 27; ++k) ks[k] = k;
-    {
-        const float sc = pack_conv16(hn.stem, stem, 0, 1, ks);
-        inv[0] = 1.0f / sc;  // accumulator holds (16 x) * (sc w): divide by sc to get 16 * y
-        for (int i = 0; i < 128; ++i) bias[i] = hn.stem.bias[i];
-    }
+    inv[0] = 1.0f / pack_stem_f16(hn.stem, 8, stem);   // accumulator holds (16 x) * (sc w): divide by sc to get 16 * y
+    for (int i = 0; i < 128; ++i) bias[i] = hn.stem.bias[i];
     for (int l = 0; l < L; ++l) {
-        const float sc = pack_conv16(hn.res[l], w, (size_t)l * layer_halfs, 36, km);
-        inv[l + 1] = 1.0f / sc;
+        inv[l + 1] = 1.0f / pack_conv16(hn.res[l], w, (size_t)l * layer_halfs);
         for (int i = 0; i < 128; ++i) bias[(size_t)(l + 1) * 128 + i] = hn.res[l].bias[i];
     }
-    OTH_HIP(hipMalloc(&mw->d_w, w.size() * 2));
-    OTH_HIP(hipMalloc(&mw->d_stem, stem.size() * 2));
-    OTH_HIP(hipMalloc(&mw->d_bias, bias.size() * 4));
-    OTH_HIP(hipMalloc(&mw->d_inv, inv.size() * 4));
-    OTH_HIP(hipMemcpy(mw->d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(mw->d_stem, stem.data(), stem.size() * 2, hipMemcpyHostToDevice));
-    if (int rc = register_scaled_bias(net, mw->d_bias, std::move(bias))) return rc;
-    OTH_HIP(hipMemcpy(mw->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    if (int rc = mw->w.upload(w)) return rc;
+    if (int rc = mw->stem.upload(stem)) return rc;
+    if (int rc = mw->bias.alloc(bias.size() * sizeof(float))) return rc;
+    if (int rc = register_scaled_bias(net, mw->bias.get(), std::move(bias))) return rc;
+    return mw->inv.upload(inv);
 }
 
-int mfma_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-                 const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->mfma, "MFMA weights not packed");
+static int mfma_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                        const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    const MfmaWeights* mw = static_cast<const MfmaWeights*>(net->trunk_w);
     MfmaArgs a;
-    a.w = net->mfma->d_w;
-    a.stem = net->mfma->d_stem;
-    a.bias = net->mfma->d_bias;
-    a.inv = net->mfma->d_inv;
-    a.n_res_layers = 2 * net->mfma->blocks;
+    a.w = mw->w.get();
+    a.stem = mw->stem.get();
+    a.bias = mw->bias.get();
+    a.inv = mw->inv.get();
+    a.n_res_layers = 2 * net->blocks;
     a.heads = net->heads;
     a.dbg = nullptr;
     a.tl = nullptr;
@@ -621,16 +572,11 @@ int mfma_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uin
     OTH_HIP(hipMalloc(&a.dbg, (size_t)dbg_grid * 4 * 8 * sizeof(unsigned long long)));
     OTH_HIP(hipMemset(a.dbg, 0, (size_t)dbg_grid * 4 * 8 * sizeof(unsigned long long)));
 #endif
-    static bool attr_set_dev[64] = {};  // per device: the attribute belongs to the (function, device) pair
-    bool& attr_set = attr_set_dev[net->device & 63];
     constexpr int kLds2 = 2 * 64 * kCellBytes + 512 + 2 * 4096;  // TP = 2: 74 240 B, two workgroups per CU
     constexpr int kLds1 = 1 * 64 * kCellBytes + 512 + 2 * 4096;  // TP = 1 (heads scratch needs the 8 KiB)
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk16<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk16<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds1));
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk16<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds2));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk16<false, 4>, net->device, kLdsBytes)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk16<true, 1>, net->device, kLds1)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk16<true, 2>, net->device, kLds2)) return rc;
     const bool x3 = net->precision == OTH_PREC_F16X3 || net->precision == OTH_PREC_F16X3_DIRECT;
     // fp16x3: two 2-position workgroups per CU; launches that cannot fill the chip (n <= 256: every workgroup has a CU to
     // itself either way) run one position per workgroup -- twice the CUs, half the MFMAs per workgroup: 0.34 -> ~0.2 ms per
@@ -676,6 +622,19 @@ int mfma_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uin
     }
 #endif
     return OTH_OK;
+}
+
+static void mfma_info(const oth_net* net, int64_t, const char** name, double* issued_per_flop, double* clamp) {
+    const bool x3 = net->precision != OTH_PREC_F16;
+    *name = x3 ? "k_trunk16 (fused ResNet forward, direct 3x3, fp16 hi/lo split)"
+               : "k_trunk16 (fused ResNet forward, direct 3x3, single fp16 pass)";
+    *issued_per_flop = (x3 ? 3.0 : 1.0) * 11.0 / 12.0;   // the all-padding row tiles of the dy = -1 / +1 taps are skipped
+    *clamp = (double)kActClamp / net->act_scale;         // 3750 at the default scale 16
+}
+
+const TrunkImpl* trunk_mfma() {
+    static const TrunkImpl row = {mfma_serves, mfma_pack, mfma_destroy, mfma_forward, mfma_info};
+    return &row;
 }
 
 }  // namespace oth

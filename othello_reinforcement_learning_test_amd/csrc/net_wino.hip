@@ -34,9 +34,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "net.h"
+#include "net_pack.h"
 #include "net_heads.h"
 #include "net_epilogue.h"
+#include "net_stamps.h"
 
 namespace oth {
 
@@ -52,13 +53,10 @@ constexpr float kWClamp = 30000.0f;           // |V| <= 2 x (activation x act_sc
                                               // <= 30000 / act_scale (1875 at the default scale 16; oth_net::act_scale)
 
 struct WinoWeights {
-    int blocks = 0;
-    uint4* d_w = nullptr;     // [layer][kk 4][xi 4][wave 8][dy 3][hi, lo][64 lanes] x 16 B   (A fragments of U)
-    uint4* d_stem = nullptr;  // [wave 8][hi, lo][64 lanes] x 16 B: direct 3x3 stem as one k-step of 32 (27 used)
-    float* d_bias = nullptr;  // [1 + 2*blocks][128], x act_scale (register_scaled_bias)
-    float* d_inv = nullptr;   // [1 + 2*blocks] 1 / weight scale
-    float* d_pfc_wt = nullptr;   // [128][65]  policy FC transposed: lanes read consecutive outputs
-    float* d_vfc1_wt = nullptr;  // [64][256]  value FC1 transposed
+    DevBuf<uint4> w;     // [layer][kk 4][xi 4][wave 8][dy 3][hi, lo][64 lanes] x 16 B   (A fragments of U)
+    DevBuf<uint4> stem;  // [wave 8][hi, lo][64 lanes] x 16 B: direct 3x3 stem as one k-step of 32 (27 used)
+    DevBuf<float> bias;  // [1 + 2*blocks][128], x act_scale (register_scaled_bias)
+    DevBuf<float> inv;   // [1 + 2*blocks] 1 / weight scale
 };
 
 struct WinoArgs {
@@ -75,22 +73,8 @@ struct WinoArgs {
     unsigned long long* dbg;   // diagnostic build (-DOTH_STAMPS) only: per-wave phase cycle sums
 };
 
-#ifdef OTH_STAMPS
-__device__ __forceinline__ unsigned long long w_clk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-__device__ __forceinline__ unsigned long long w_realclk() {   // 100 MHz constant clock
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define OTH_WSTAMP(i) { const unsigned long long t1_ = w_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
+#ifdef OTH_STAMPS   // net_stamps.h
+#define OTH_WSTAMP(i) { const unsigned long long t1_ = oth_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
 #else
 #define OTH_WSTAMP(i)
 #endif
@@ -132,8 +116,8 @@ __device__ __forceinline__ void heads_block2(const HeadParams& hp, const float* 
                                              unsigned long long* hst = nullptr) {
     const int t = threadIdx.x;
 #ifdef OTH_STAMPS
-    unsigned long long h0_ = w_clk();
-#define OTH_HST(i) { const unsigned long long h1_ = w_clk(); if (hst) hst[i] = h1_ - h0_; h0_ = h1_; }
+    unsigned long long h0_ = oth_clk();
+#define OTH_HST(i) { const unsigned long long h1_ = oth_clk(); if (hst) hst[i] = h1_ - h0_; h0_ = h1_; }
 #else
 #define OTH_HST(i)
 #endif
@@ -226,7 +210,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
                                                     float* __restrict__ logp, float* __restrict__ vout) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
 #ifdef OTH_STAMPS
-    const unsigned long long tentry_ = w_clk();
+    const unsigned long long tentry_ = oth_clk();
 #endif
     int64_t nv = n;
     if (n_valid) {
@@ -340,8 +324,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
     static_assert((NG * 6) % NRING == 0, "the ring slot must be a compile-time function of (group, fragment)");
     uint4 wq[NRING];
 #ifdef OTH_STAMPS
-    unsigned long long ph_[4] = {0, 0, 0, 0}, t0_ = w_clk(), tstart_ = t0_;
-    const unsigned long long rstart_ = w_realclk();
+    unsigned long long ph_[4] = {0, 0, 0, 0}, t0_ = oth_clk(), tstart_ = t0_;
+    const unsigned long long rstart_ = oth_realclk();
 #endif
     float4 b4 = *(const float4*)(a.bias + ch0), b4n = b4;   // bias (x act_scale) and 1 / weight scale of the layer in the epilogue
     float inv = a.inv[0], invn = inv;
@@ -524,12 +508,12 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
     if (a.dbg && lane == 0) {
         unsigned long long* o = a.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
         for (int i = 0; i < 4; ++i) o[i] = ph_[i];
-        o[4] = w_clk() - tstart_;
-        o[5] = w_realclk() - rstart_;
+        o[4] = oth_clk() - tstart_;
+        o[5] = oth_realclk() - rstart_;
         o[6] = rstart_;
         o[7] = tstart_ - tentry_;   // prologue + stem
     }
-    const unsigned long long theads_ = w_clk();
+    const unsigned long long theads_ = oth_clk();
 #endif
 
     // ---------------- heads (fp32 VALU): final activations (in `res`, x act_scale) -> LDS [128 cells][128] f32, then the
@@ -552,13 +536,13 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
     __syncthreads();
 #ifdef OTH_STAMPS
     unsigned long long hst_[2] = {0, 0};
-    const unsigned long long tpre_ = w_clk() - theads_;   // res -> LDS planes + barriers
+    const unsigned long long tpre_ = oth_clk() - theads_;   // res -> LDS planes + barriers
     heads_block2(a.heads, a.pfc_wt, a.vfc1_wt, (const float*)lds, (float*)(lds + 128 * kHeadRow * 4 + 64), TP == 2 && pos0 + 1 < nv,
                  logp + pos0 * 65, vout + pos0, hst_);
 #if OTH_STAMPS != 2   // -DOTH_STAMPS=2 keeps the layer phases (weight prefetch | barriers | epilogue | conv) instead
     if (a.dbg && lane == 0) {
         unsigned long long* o = a.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
-        o[3] = w_clk() - theads_;   // (overwrites the conv sum)
+        o[3] = oth_clk() - theads_;   // (overwrites the conv sum)
         o[0] = tpre_; o[1] = hst_[0]; o[2] = hst_[1];   // (overwrite prefetch / barriers / epilogue sums)
     }
 #endif
@@ -571,75 +555,32 @@ __global__ __launch_bounds__(512, 2) void k_trunk_w(WinoArgs a, const uint64_t* 
 // ------------------------------------------------------------------------------------------------
 // host: transformed weights in A-fragment order
 // ------------------------------------------------------------------------------------------------
-static inline void wsplit(float v, uint16_t& hi, uint16_t& lo) {
-    const _Float16 hh = (_Float16)v;
-    const _Float16 ll = (_Float16)(v - (float)hh);
-    memcpy(&hi, &hh, 2);
-    memcpy(&lo, &ll, 2);
+// A 128-filter 8x8 network in f16x3 (1.375x fewer MFMAs than k_trunk16, +9 % games/s on the bench); OTH_WINO=0, read when
+// the weights are loaded, leaves it to the direct kernel -- the A/B switch.
+static bool wino_serves(const oth_net* net, int precision) {
+    const char* e = getenv("OTH_WINO");
+    return precision == OTH_PREC_F16X3 && net->filters == 128 && net->board == 8 && !(e && atoi(e) == 0);
 }
 
-void wino_free_weights(oth_net* net) {
-    if (!net->wino) return;
-    WinoWeights* w = net->wino;
-    if (w->d_w) (void)hipFree(w->d_w);
-    if (w->d_stem) (void)hipFree(w->d_stem);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_inv) (void)hipFree(w->d_inv);
-    if (w->d_pfc_wt) (void)hipFree(w->d_pfc_wt);
-    if (w->d_vfc1_wt) (void)hipFree(w->d_vfc1_wt);
-    delete w;
-    net->wino = nullptr;
-}
+static void wino_destroy(void* w) { delete static_cast<WinoWeights*>(w); }
 
-int wino_pack_weights(oth_net* net) {
+static int wino_pack(oth_net* net) {
     const HostNet& hn = net->host;
     OTH_CHECK(hn.filters == 128 && hn.board == 8, "the Winograd trunk is built for 128 filters on 8x8");
     const int L = 2 * hn.blocks;
     WinoWeights* ww = new WinoWeights();
-    ww->blocks = hn.blocks;
-    net->wino = ww;
+    net->trunk_w = ww;
     const size_t frag = 64 * 8;                              // halfs per fragment
     const size_t layer_halfs = (size_t)16 * 8 * 6 * frag;    // 16 groups (kk, xi) x 8 waves x (3 dy x hi/lo): the order the
                                                              // kernel streams them in, one ascending run per wave
-    std::vector<uint16_t> w((size_t)L * layer_halfs + 6 * 8 * 6 * frag), stem((size_t)8 * 2 * frag);   // + zero groups: the last conv's look-ahead (at most 31 fragments = 6 groups)
+    std::vector<uint16_t> w((size_t)L * layer_halfs + 6 * 8 * 6 * frag), stem;   // + zero groups: the last conv's look-ahead (at most 31 fragments = 6 groups)
     std::vector<float> bias((size_t)(L + 1) * 128), inv(L + 1);
-    {   // stem: direct, gemm k = tap*3 + plane (27 of 32), rows = 16 channels of a wave
-        const FoldedConv& cv = hn.stem;
-        float mx = 0.f;
-        for (float x : cv.w) mx = fmaxf(mx, fabsf(x));
-        int e = mx > 0.f ? (int)floorf(log2f(16384.0f / mx)) : 0;
-        e = e > 24 ? 24 : (e < -24 ? -24 : e);
-        const float scale = ldexpf(1.0f, e);
-        for (int wv = 0; wv < 8; ++wv)
-            for (int l = 0; l < 64; ++l)
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int k = 8 * (l >> 4) + jj, co = 16 * wv + (l & 15);
-                    const float v = k < 27 ? cv.w[(size_t)k * cv.cout + co] * scale : 0.f;   // [tap][cin=3][cout]: k = tap*3 + plane
-                    uint16_t hi, lo;
-                    wsplit(v, hi, lo);
-                    stem[((size_t)wv * 2 + 0) * frag + (size_t)l * 8 + jj] = hi;
-                    stem[((size_t)wv * 2 + 1) * frag + (size_t)l * 8 + jj] = lo;
-                }
-        inv[0] = 1.0f / scale;
-        for (int i = 0; i < 128; ++i) bias[i] = cv.bias[i];
-    }
-    static const double G[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
-    std::vector<double> U((size_t)3 * 4 * 128 * 128);   // [dy][xi][ci][co]
+    inv[0] = 1.0f / pack_stem_f16(hn.stem, 8, stem);
+    for (int i = 0; i < 128; ++i) bias[i] = hn.stem.bias[i];
+    std::vector<double> U;   // [dy][xi][ci][co]
     for (int li = 0; li < L; ++li) {
         const FoldedConv& cv = hn.res[li];
-        double mx = 0.0;
-        for (int d = 0; d < 3; ++d)
-            for (int xi = 0; xi < 4; ++xi)
-                for (int ci = 0; ci < 128; ++ci)
-                    for (int co = 0; co < 128; ++co) {
-                        double u = 0.0;
-                        for (int i = 0; i < 3; ++i) u += G[xi][i] * (double)cv.w[((size_t)(d * 3 + i) * 128 + ci) * 128 + co];
-                        U[(((size_t)d * 4 + xi) * 128 + ci) * 128 + co] = u;
-                        mx = fmax(mx, fabs(u));
-                    }
-        int e = mx > 0.0 ? (int)floor(log2(16384.0 / mx)) : 0;
-        e = e > 24 ? 24 : (e < -24 ? -24 : e);
-        const double scale = ldexp(1.0, e);
+        const double scale = pow2_weight_scale(winograd_f23_U(cv, 128, U));
         for (int d = 0; d < 3; ++d)
             for (int kk = 0; kk < 4; ++kk)
                 for (int wv = 0; wv < 8; ++wv)
@@ -649,7 +590,7 @@ int wino_pack_weights(oth_net* net) {
                                 const int ci = 32 * kk + 8 * (l >> 4) + jj, co = 16 * wv + (l & 15);
                                 const float v = (float)(U[(((size_t)d * 4 + xi) * 128 + ci) * 128 + co] * scale);
                                 uint16_t hi, lo;
-                                wsplit(v, hi, lo);
+                                split_f16(v, hi, lo);
                                 const size_t f0 = (size_t)li * layer_halfs + ((((size_t)(kk * 4 + xi) * 8 + wv) * 3 + d) * 2) * frag;
                                 w[f0 + (size_t)l * 8 + jj] = hi;
                                 w[f0 + frag + (size_t)l * 8 + jj] = lo;
@@ -657,47 +598,34 @@ int wino_pack_weights(oth_net* net) {
         inv[li + 1] = (float)(1.0 / scale);
         for (int i = 0; i < 128; ++i) bias[(size_t)(li + 1) * 128 + i] = cv.bias[i];
     }
-    std::vector<float> pt((size_t)128 * 65), vt((size_t)64 * 256);
-    for (int o = 0; o < 65; ++o)
-        for (int i = 0; i < 128; ++i) pt[(size_t)i * 65 + o] = hn.pfc_w[(size_t)o * 128 + i];
-    for (int o = 0; o < 256; ++o)
-        for (int i = 0; i < 64; ++i) vt[(size_t)i * 256 + o] = hn.vfc1_w[(size_t)o * 64 + i];
-    OTH_HIP(hipMalloc(&ww->d_pfc_wt, pt.size() * 4));
-    OTH_HIP(hipMalloc(&ww->d_vfc1_wt, vt.size() * 4));
-    OTH_HIP(hipMemcpy(ww->d_pfc_wt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(ww->d_vfc1_wt, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMalloc(&ww->d_w, w.size() * 2));
-    OTH_HIP(hipMalloc(&ww->d_stem, stem.size() * 2));
-    OTH_HIP(hipMalloc(&ww->d_bias, bias.size() * 4));
-    OTH_HIP(hipMalloc(&ww->d_inv, inv.size() * 4));
-    OTH_HIP(hipMemcpy(ww->d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(ww->d_stem, stem.data(), stem.size() * 2, hipMemcpyHostToDevice));
-    if (int rc = register_scaled_bias(net, ww->d_bias, std::move(bias))) return rc;
-    OTH_HIP(hipMemcpy(ww->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    if (int rc = ww->w.upload(w)) return rc;
+    if (int rc = ww->stem.upload(stem)) return rc;
+    if (int rc = ww->bias.alloc(bias.size() * sizeof(float))) return rc;
+    if (int rc = register_scaled_bias(net, ww->bias.get(), std::move(bias))) return rc;
+    return ww->inv.upload(inv);
 }
 
 // Launches that cannot fill the chip (every workgroup has a CU to itself either way) run one position per workgroup; both
 // builds sum every accumulator in the same order, so a position's outputs do not depend on this.  OTH_WINO_TP=1|2 (read
 // per call) forces a build: the switch the variants test uses to compare the two on the same batch.  The ONE place the
-// decision is made: oth_net_kernel_info reports what this returns.
-int wino_positions_per_workgroup(int64_t n) {
+// decision is made: wino_info reports what this returns.
+static int wino_positions_per_workgroup(int64_t n) {
     const char* tpe = getenv("OTH_WINO_TP");
     return tpe ? (atoi(tpe) == 1 ? 1 : 2) : (n <= 256 ? 1 : 2);
 }
 
-int wino_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-                 const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->wino, "Winograd weights not packed");
+static int wino_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                        const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    const WinoWeights* ww = static_cast<const WinoWeights*>(net->trunk_w);
     WinoArgs a;
-    a.w = net->wino->d_w;
-    a.stem = net->wino->d_stem;
-    a.bias = net->wino->d_bias;
-    a.inv = net->wino->d_inv;
-    a.n_res_layers = 2 * net->wino->blocks;
+    a.w = ww->w.get();
+    a.stem = ww->stem.get();
+    a.bias = ww->bias.get();
+    a.inv = ww->inv.get();
+    a.n_res_layers = 2 * net->blocks;
     a.heads = net->heads;
-    a.pfc_wt = net->wino->d_pfc_wt;
-    a.vfc1_wt = net->wino->d_vfc1_wt;
+    a.pfc_wt = net->d_pfc_wt;
+    a.vfc1_wt = net->d_vfc1_wt;
     a.sat = net->d_sat;
     a.act_scale = net->act_scale;
     a.dbg = nullptr;
@@ -706,13 +634,8 @@ int wino_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uin
     OTH_HIP(hipMalloc(&a.dbg, (size_t)dbg_grid * 8 * 8 * sizeof(unsigned long long)));
     OTH_HIP(hipMemset(a.dbg, 0, (size_t)dbg_grid * 8 * 8 * sizeof(unsigned long long)));
 #endif
-    static bool attr_set_dev[64] = {};
-    bool& attr_set = attr_set_dev[net->device & 63];
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_w<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kWLds));
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_w<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kWLds));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_w<1>, net->device, kWLds)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_w<2>, net->device, kWLds)) return rc;
     const int tp = wino_positions_per_workgroup(n);
     const unsigned grid = (unsigned)((n + tp - 1) / tp);
     if (tp == 1) hipLaunchKernelGGL(k_trunk_w<1>, dim3(grid), dim3(512), kWLds, stream, a, sb, ob, lg, n, n_valid, logp, v);
@@ -747,6 +670,19 @@ int wino_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uin
     }
 #endif
     return OTH_OK;
+}
+
+static void wino_info(const oth_net* net, int64_t n, const char** name, double* issued_per_flop, double* clamp) {
+    *name = wino_positions_per_workgroup(n) == 2
+                ? "k_trunk_w<2> (fused ResNet forward, 1-D Winograd F(2,3) residual convolutions, two positions per workgroup)"
+                : "k_trunk_w<1> (fused ResNet forward, 1-D Winograd F(2,3) residual convolutions, one position per workgroup)";
+    *issued_per_flop = 3.0 * 2.0 / 3.0;   // three split products, 4 multiplies per 2 outputs instead of 6
+    *clamp = (double)kWClamp / net->act_scale;   // 1875 at the default scale 16
+}
+
+const TrunkImpl* trunk_wino() {
+    static const TrunkImpl row = {wino_serves, wino_pack, wino_destroy, wino_forward, wino_info};
+    return &row;
 }
 
 }  // namespace oth

@@ -25,9 +25,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "net.h"
+#include "net_pack.h"
 #include "net_heads_wave.h"
 #include "net_epilogue.h"
+#include "net_stamps.h"
 
 namespace oth {
 
@@ -51,13 +52,10 @@ constexpr int k6Groups = 6;                     // (row tap d, k-step kk of 32 i
 constexpr int k6GroupU4 = 4 * 8 * 64;           // uint4 per group: 4 waves x 8 fragments x 64 lanes
 
 struct Wino6Weights {
-    int blocks = 0;
-    uint4* d_w = nullptr;     // [layer][group 6][wave 4][xi 4][hi, lo][64 lanes] x 16 B   (A fragments of U)
-    uint4* d_stem = nullptr;  // [wave 4][hi, lo][64 lanes] x 16 B: direct 3x3 stem as one k-step of 32 (27 used)
-    float* d_bias = nullptr;  // [1 + 2*blocks][64], x act_scale (register_scaled_bias)
-    float* d_inv = nullptr;   // [1 + 2*blocks] 1 / weight scale
-    float* d_pfc_wt = nullptr;   // [72][37]  policy FC transposed (net_heads_wave.h)
-    float* d_vfc1_wt = nullptr;  // [36][256] value FC1 transposed
+    DevBuf<uint4> w;     // [layer][group 6][wave 4][xi 4][hi, lo][64 lanes] x 16 B   (A fragments of U)
+    DevBuf<uint4> stem;  // [wave 4][hi, lo][64 lanes] x 16 B: direct 3x3 stem as one k-step of 32 (27 used)
+    DevBuf<float> bias;  // [1 + 2*blocks][64], x act_scale (register_scaled_bias)
+    DevBuf<float> inv;   // [1 + 2*blocks] 1 / weight scale
 };
 
 struct Wino6Args {
@@ -74,22 +72,8 @@ struct Wino6Args {
     unsigned long long* dbg;   // diagnostic build (-DOTH_STAMPS) only: per-wave phase cycle sums
 };
 
-#ifdef OTH_STAMPS
-__device__ __forceinline__ unsigned long long w6_clk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-__device__ __forceinline__ unsigned long long w6_realclk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define OTH_W6STAMP(i) { const unsigned long long t1_ = w6_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
+#ifdef OTH_STAMPS   // net_stamps.h
+#define OTH_W6STAMP(i) { const unsigned long long t1_ = oth_clk(); ph_[i] += t1_ - t0_; t0_ = t1_; }
 #else
 #define OTH_W6STAMP(i)
 #endif
@@ -131,8 +115,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(k6Regs))) void 
     const int64_t pos0 = (int64_t)blockIdx.x * k6TP;
     if (pos0 >= nv) return;
 #ifdef OTH_STAMPS
-    unsigned long long ph_[5] = {0, 0, 0, 0, 0}, t0_ = w6_clk();   // prologue + stem | barrier waits | epilogues | convolutions | heads
-    const unsigned long long tstart_ = t0_, rstart_ = w6_realclk();
+    unsigned long long ph_[5] = {0, 0, 0, 0, 0}, t0_ = oth_clk();   // prologue + stem | barrier waits | epilogues | convolutions | heads
+    const unsigned long long tstart_ = t0_, rstart_ = oth_realclk();
 #endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g4 = lane >> 4, c = lane & 15;
@@ -424,8 +408,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(k6Regs))) void 
     if (a.dbg && lane == 0) {
         unsigned long long* o = a.dbg + ((size_t)blockIdx.x * 4 + wave) * 8;
         for (int i = 0; i < 5; ++i) o[i] = ph_[i];
-        o[5] = w6_clk() - tstart_;
-        o[6] = w6_realclk() - rstart_;
+        o[5] = oth_clk() - tstart_;
+        o[6] = oth_realclk() - rstart_;
     }
 #endif
 }
@@ -433,74 +417,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(k6Regs))) void 
 // ------------------------------------------------------------------------------------------------
 // host: transformed weights in A-fragment order
 // ------------------------------------------------------------------------------------------------
-static inline void w6split(float v, uint16_t& hi, uint16_t& lo) {
-    const _Float16 hh = (_Float16)v;
-    const _Float16 ll = (_Float16)(v - (float)hh);
-    memcpy(&hi, &hh, 2);
-    memcpy(&lo, &ll, 2);
+// A 64-filter 6x6 network (BASELINE configs[4]) in f16x3 (1.5x fewer MFMAs than k_trunk_h3 and no padded cells);
+// OTH_WINO6=0, read when the weights are loaded, leaves it to k_trunk_h3 -- the A/B switch.
+static bool wino6_serves(const oth_net* net, int precision) {
+    const char* e = getenv("OTH_WINO6");
+    return precision == OTH_PREC_F16X3 && net->filters == k6F && net->board == k6BS && !(e && atoi(e) == 0);
 }
 
-void wino6_free_weights(oth_net* net) {
-    if (!net->wino6) return;
-    Wino6Weights* w = net->wino6;
-    if (w->d_w) (void)hipFree(w->d_w);
-    if (w->d_stem) (void)hipFree(w->d_stem);
-    if (w->d_bias) (void)hipFree(w->d_bias);
-    if (w->d_inv) (void)hipFree(w->d_inv);
-    if (w->d_pfc_wt) (void)hipFree(w->d_pfc_wt);
-    if (w->d_vfc1_wt) (void)hipFree(w->d_vfc1_wt);
-    delete w;
-    net->wino6 = nullptr;
-}
+static void wino6_destroy(void* w) { delete static_cast<Wino6Weights*>(w); }
 
-int wino6_pack_weights(oth_net* net) {
+static int wino6_pack(oth_net* net) {
     const HostNet& hn = net->host;
     OTH_CHECK(hn.filters == k6F && hn.board == k6BS, "the 6x6 Winograd trunk is built for 64 filters on 6x6");
     const int L = 2 * hn.blocks;
     Wino6Weights* ww = new Wino6Weights();
-    ww->blocks = hn.blocks;
-    net->wino6 = ww;
+    net->trunk_w = ww;
     const size_t frag = 64 * 8;                                     // halfs per fragment
     const size_t layer_halfs = (size_t)k6Groups * 4 * 8 * frag;     // 6 groups x 4 waves x (4 xi x hi/lo)
-    std::vector<uint16_t> w((size_t)L * layer_halfs + 4 * 8 * frag), stem((size_t)4 * 2 * frag);   // + one zero group
+    std::vector<uint16_t> w((size_t)L * layer_halfs + 4 * 8 * frag), stem;   // + one zero group
     std::vector<float> bias((size_t)(L + 1) * k6F), inv(L + 1);
-    {   // stem: direct, gemm k = tap*3 + plane (27 of 32), rows = 16 channels of a wave
-        const FoldedConv& cv = hn.stem;
-        float mx = 0.f;
-        for (float x : cv.w) mx = fmaxf(mx, fabsf(x));
-        int e = mx > 0.f ? (int)floorf(log2f(16384.0f / mx)) : 0;
-        e = e > 24 ? 24 : (e < -24 ? -24 : e);
-        const float scale = ldexpf(1.0f, e);
-        for (int wv = 0; wv < 4; ++wv)
-            for (int l = 0; l < 64; ++l)
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int k = 8 * (l >> 4) + jj, co = 16 * wv + (l & 15);
-                    const float v = k < 27 ? cv.w[(size_t)k * cv.cout + co] * scale : 0.f;   // [tap][cin=3][cout]
-                    uint16_t hi, lo;
-                    w6split(v, hi, lo);
-                    stem[((size_t)wv * 2 + 0) * frag + (size_t)l * 8 + jj] = hi;
-                    stem[((size_t)wv * 2 + 1) * frag + (size_t)l * 8 + jj] = lo;
-                }
-        inv[0] = 1.0f / scale;
-        for (int i = 0; i < k6F; ++i) bias[i] = cv.bias[i];
-    }
-    static const double G[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
-    std::vector<double> U((size_t)3 * 4 * k6F * k6F);   // [dy][xi][ci][co]
+    inv[0] = 1.0f / pack_stem_f16(hn.stem, 4, stem);
+    for (int i = 0; i < k6F; ++i) bias[i] = hn.stem.bias[i];
+    std::vector<double> U;   // [dy][xi][ci][co]
     for (int li = 0; li < L; ++li) {
         const FoldedConv& cv = hn.res[li];
-        double mx = 0.0;
-        for (int d = 0; d < 3; ++d)
-            for (int xi = 0; xi < 4; ++xi)
-                for (int ci = 0; ci < k6F; ++ci)
-                    for (int co = 0; co < k6F; ++co) {
-                        double u = 0.0;
-                        for (int i = 0; i < 3; ++i) u += G[xi][i] * (double)cv.w[((size_t)(d * 3 + i) * k6F + ci) * k6F + co];
-                        U[(((size_t)d * 4 + xi) * k6F + ci) * k6F + co] = u;
-                        mx = fmax(mx, fabs(u));
-                    }
-        int e = mx > 0.0 ? (int)floor(log2(16384.0 / mx)) : 0;
-        e = e > 24 ? 24 : (e < -24 ? -24 : e);
-        const double scale = ldexp(1.0, e);
+        const double scale = pow2_weight_scale(winograd_f23_U(cv, k6F, U));
         for (int d = 0; d < 3; ++d)
             for (int kk = 0; kk < 2; ++kk)
                 for (int wv = 0; wv < 4; ++wv)
@@ -510,7 +451,7 @@ int wino6_pack_weights(oth_net* net) {
                                 const int ci = 32 * kk + 8 * (l >> 4) + jj, co = 16 * wv + (l & 15);
                                 const float v = (float)(U[(((size_t)d * 4 + xi) * k6F + ci) * k6F + co] * scale);
                                 uint16_t hi, lo;
-                                w6split(v, hi, lo);
+                                split_f16(v, hi, lo);
                                 const size_t f0 = (size_t)li * layer_halfs + ((((size_t)(d * 2 + kk) * 4 + wv) * 4 + xi) * 2) * frag;
                                 w[f0 + (size_t)l * 8 + jj] = hi;
                                 w[f0 + frag + (size_t)l * 8 + jj] = lo;
@@ -518,47 +459,29 @@ int wino6_pack_weights(oth_net* net) {
         inv[li + 1] = (float)(1.0 / scale);
         for (int i = 0; i < k6F; ++i) bias[(size_t)(li + 1) * k6F + i] = cv.bias[i];
     }
-    std::vector<float> pt((size_t)2 * k6Cells * k6NP), vt((size_t)k6Cells * 256);
-    for (int o = 0; o < k6NP; ++o)
-        for (int i = 0; i < 2 * k6Cells; ++i) pt[(size_t)i * k6NP + o] = hn.pfc_w[(size_t)o * 2 * k6Cells + i];
-    for (int o = 0; o < 256; ++o)
-        for (int i = 0; i < k6Cells; ++i) vt[(size_t)i * 256 + o] = hn.vfc1_w[(size_t)o * k6Cells + i];
-    OTH_HIP(hipMalloc(&ww->d_pfc_wt, pt.size() * 4));
-    OTH_HIP(hipMalloc(&ww->d_vfc1_wt, vt.size() * 4));
-    OTH_HIP(hipMalloc(&ww->d_w, w.size() * 2));
-    OTH_HIP(hipMalloc(&ww->d_stem, stem.size() * 2));
-    OTH_HIP(hipMalloc(&ww->d_bias, bias.size() * 4));
-    OTH_HIP(hipMalloc(&ww->d_inv, inv.size() * 4));
-    OTH_HIP(hipMemcpy(ww->d_pfc_wt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(ww->d_vfc1_wt, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(ww->d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-    OTH_HIP(hipMemcpy(ww->d_stem, stem.data(), stem.size() * 2, hipMemcpyHostToDevice));
-    if (int rc = register_scaled_bias(net, ww->d_bias, std::move(bias))) return rc;
-    OTH_HIP(hipMemcpy(ww->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    return OTH_OK;
+    if (int rc = ww->w.upload(w)) return rc;
+    if (int rc = ww->stem.upload(stem)) return rc;
+    if (int rc = ww->bias.alloc(bias.size() * sizeof(float))) return rc;
+    if (int rc = register_scaled_bias(net, ww->bias.get(), std::move(bias))) return rc;
+    return ww->inv.upload(inv);
 }
 
-int wino6_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
-                  const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
-    OTH_CHECK(net->wino6, "6x6 Winograd weights not packed");
+static int wino6_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const uint64_t* lg, int64_t n,
+                         const int32_t* n_valid, float* logp, float* v, hipStream_t stream) {
+    const Wino6Weights* ww = static_cast<const Wino6Weights*>(net->trunk_w);
     Wino6Args a;
     memset(&a, 0, sizeof(a));
-    a.w = net->wino6->d_w;
-    a.stem = net->wino6->d_stem;
-    a.bias = net->wino6->d_bias;
-    a.inv = net->wino6->d_inv;
-    a.n_res_layers = 2 * net->wino6->blocks;
+    a.w = ww->w.get();
+    a.stem = ww->stem.get();
+    a.bias = ww->bias.get();
+    a.inv = ww->inv.get();
+    a.n_res_layers = 2 * net->blocks;
     a.heads = net->heads;
-    a.pfc_wt = net->wino6->d_pfc_wt;
-    a.vfc1_wt = net->wino6->d_vfc1_wt;
+    a.pfc_wt = net->d_pfc_wt;
+    a.vfc1_wt = net->d_vfc1_wt;
     a.sat = net->d_sat;
     a.act_scale = net->act_scale;
-    static bool attr_set_dev[64] = {};
-    bool& attr_set = attr_set_dev[net->device & 63];
-    if (!attr_set) {
-        OTH_HIP(hipFuncSetAttribute((const void*)k_trunk_w6, hipFuncAttributeMaxDynamicSharedMemorySize, k6Lds));
-        attr_set = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)k_trunk_w6, net->device, k6Lds)) return rc;
     const unsigned grid = (unsigned)((n + k6TP - 1) / k6TP);
 #ifdef OTH_STAMPS
     OTH_HIP(hipMalloc(&a.dbg, (size_t)grid * 4 * 8 * sizeof(unsigned long long)));
@@ -584,6 +507,17 @@ int wino6_forward(oth_net* net, const uint64_t* sb, const uint64_t* ob, const ui
     hipLaunchKernelGGL(k_trunk_w6, dim3(grid), dim3(256), k6Lds, stream, a, sb, ob, lg, n, n_valid, logp, v);
     OTH_HIP(hipGetLastError());
     return OTH_OK;
+}
+
+static void wino6_info(const oth_net* net, int64_t, const char** name, double* issued_per_flop, double* clamp) {
+    *name = "k_trunk_w6 (fused ResNet forward, 6x6, 1-D Winograd F(2,3) residual convolutions, eight positions per workgroup)";
+    *issued_per_flop = 3.0 * 2.0 / 3.0;   // three split products, 4 multiplies per 2 outputs instead of 6, every N-tile full
+    *clamp = (double)k6Clamp / net->act_scale;   // 1875 at the default scale 16
+}
+
+const TrunkImpl* trunk_wino6() {
+    static const TrunkImpl row = {wino6_serves, wino6_pack, wino6_destroy, wino6_forward, wino6_info};
+    return &row;
 }
 
 }  // namespace oth

@@ -30,27 +30,36 @@ def pkg():
     return p
 
 
-def _b(prec, filters, board, kernel, clamp16=0.0, **env):
-    return {"prec": prec, "filters": filters, "board": board, "kernel": kernel, "clamp16": clamp16, "env": env}
+def _b(prec, filters, board, kernel, issued, clamp16=0.0, **env):
+    return {"prec": prec, "filters": filters, "board": board, "kernel": kernel, "issued": issued, "clamp16": clamp16, "env": env}
 
 
-# every trunk build the library can dispatch: name -> how it is selected, what kernel_info must report, its clamp at scale 16
+def _h3_issued(positions_per_wave, board):
+    """three split products over N-tiles of 16 cells that cover the P positions of a wave: 3 * ceil16(P * cells) / (P * cells)"""
+    cells = positions_per_wave * board * board
+    return 3 * ((cells + 15) // 16 * 16) / cells
+
+
+# every trunk build the library can dispatch: name -> how it is selected, what kernel_info must report (the kernel, the MFMA
+# FLOPs it issues per algorithmic FLOP -- bench.py's roofline multiplies by that figure -- and its clamp at scale 16)
 BUILDS = {}
 for _bs in (8, 6):
     for _f in (16, 32, 64, 128):
-        BUILDS["f32-%d-%dx%d" % (_f, _bs, _bs)] = _b("f32", _f, _bs, "k_trunk_f32")
+        BUILDS["f32-%d-%dx%d" % (_f, _bs, _bs)] = _b("f32", _f, _bs, "k_trunk_f32", 1.0)
 BUILDS.update({
-    "h3-32-8x8": _b("f16x3", 32, 8, "k_trunk_h3", 3750.0),
-    "h3-64-8x8": _b("f16x3", 64, 8, "k_trunk_h3", 3750.0),
-    "h3-32-6x6": _b("f16x3", 32, 6, "k_trunk_h3", 3750.0),
-    "h3-128-6x6": _b("f16x3", 128, 6, "k_trunk_h3", 3750.0),
-    "h3-64-6x6": _b("f16x3", 64, 6, "k_trunk_h3", 3750.0, OTH_WINO6="0"),     # read when the weights are packed
-    "w6-64-6x6": _b("f16x3", 64, 6, "k_trunk_w6", 1875.0),
-    "direct-tp1": _b("f16x3_direct", 128, 8, "k_trunk16", 3750.0, OTH_TRUNK_TP="1"),   # read per launch; kernel_info cannot
-    "direct-tp2": _b("f16x3_direct", 128, 8, "k_trunk16", 3750.0, OTH_TRUNK_TP="2"),   # see it: bit-identity test below
-    "wino-tp1": _b("f16x3", 128, 8, "k_trunk_w<1>", 1875.0, OTH_WINO_TP="1"),
-    "wino-tp2": _b("f16x3", 128, 8, "k_trunk_w<2>", 1875.0, OTH_WINO_TP="2"),
+    # k_trunk_h3: one position per wave on 8x8 (3.0) and for 128 filters on 6x6 (4.0); on 6x6 two with 64 filters (10/3), four with 32 (3.0)
+    "h3-32-8x8": _b("f16x3", 32, 8, "k_trunk_h3", _h3_issued(1, 8), 3750.0),
+    "h3-64-8x8": _b("f16x3", 64, 8, "k_trunk_h3", _h3_issued(1, 8), 3750.0),
+    "h3-32-6x6": _b("f16x3", 32, 6, "k_trunk_h3", _h3_issued(4, 6), 3750.0),
+    "h3-128-6x6": _b("f16x3", 128, 6, "k_trunk_h3", _h3_issued(1, 6), 3750.0),
+    "h3-64-6x6": _b("f16x3", 64, 6, "k_trunk_h3", _h3_issued(2, 6), 3750.0, OTH_WINO6="0"),     # read when the weights are packed
+    "w6-64-6x6": _b("f16x3", 64, 6, "k_trunk_w6", 2.0, 1875.0),
+    "direct-tp1": _b("f16x3_direct", 128, 8, "k_trunk16", 2.75, 3750.0, OTH_TRUNK_TP="1"),   # read per launch; kernel_info cannot
+    "direct-tp2": _b("f16x3_direct", 128, 8, "k_trunk16", 2.75, 3750.0, OTH_TRUNK_TP="2"),   # see it: bit-identity test below
+    "wino-tp1": _b("f16x3", 128, 8, "k_trunk_w<1>", 2.0, 1875.0, OTH_WINO_TP="1"),
+    "wino-tp2": _b("f16x3", 128, 8, "k_trunk_w<2>", 2.0, 1875.0, OTH_WINO_TP="2"),
 })
+assert [_h3_issued(1, 8), _h3_issued(2, 6), _h3_issued(4, 6), _h3_issued(1, 6)] == [3.0, 10 / 3, 3.0, 4.0]
 SPLIT_BUILDS = [k for k, b in BUILDS.items() if b["prec"] != "f32"]
 
 
@@ -124,6 +133,7 @@ def _run_build(pkg, shared, build, case):
         info = ev.kernel_info(len(x))
         assert info["kernel"].startswith(b["kernel"]), (build, info["kernel"])      # the intended kernel, not one tested twice
         assert info["clamp"] == b["clamp16"]
+        assert info["issued_per_flop"] == b["issued"], (build, info["issued_per_flop"])
         logp, v = ev.forward_planes(x, rescue=False)
         torch.cuda.synchronize()
         logp, v = logp.clone(), v.clone()
