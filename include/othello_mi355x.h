@@ -225,12 +225,38 @@ typedef struct {
                                   OTH_RULES_OTHELLO (1): every rules call of the search and of self-play (legal moves,
                                   flips, end of game) follows standard Othello; the search semantics, the RNG, the cache
                                   and the tuple layout are the same.  Any other value: oth_engine_create fails. */
+    int32_t search;            /* OTH_SEARCH_REFERENCE (0): the reference's search, today's behaviour bit for bit (SURVEY 8.1:
+                                  a child's value sum is kept from the view of the side to move AT the child and maximised
+                                  un-negated, the root is never counted, z has the reference's sign).
+                                  OTH_SEARCH_ALPHAZERO (1): the search an AlphaZero trainer expects --
+                                    backup: an edge accumulates the value from the view of the side that CHOSE it (leaf value v:
+                                      the leaf edge gets -v, its parent's +v, ...);
+                                    parent count: the root's is 1 + the simulations backed up so far (an interior node's is the
+                                      visit count of the edge into it, as before), so root priors and root noise matter;
+                                    z[p] = outcome from the view of the side to move at ply p;
+                                    root Dirichlet noise is generated on the device when asked for (oth_engine_set_root_noise,
+                                      add_noise of oth_selfplay_run) and dirichlet_epsilon > 0.
+                                  Masking, renormalisation, float32 c_puct * P, float64 scores, first maximum on ties, one leaf
+                                  per simulation, the RNG of the action draws and the tuple layout are the same.  Independent of
+                                  `rules`.  Any other value: oth_engine_create fails. */
 } oth_engine_cfg;
+#define OTH_SEARCH_REFERENCE 0
+#define OTH_SEARCH_ALPHAZERO 1
 
 oth_engine *oth_engine_create(const oth_engine_cfg *cfg);
 void oth_engine_destroy(oth_engine *e);
 /* evaluator used by oth_search_run / oth_selfplay_run (not owned) */
 int oth_engine_set_net(oth_engine *e, oth_net *net);
+/* Root Dirichlet noise of the step-wise search, the lock-step run and the stream (the 79th entry point of this header;
+ * no reference counterpart: mcts.py:220-221 draws np.random.dirichlet on the host, and under the reference's search the
+ * draw cannot change a result).  enable != 0: every root expanded from now on gets P' = (float)((1 - eps) * P + eps * eta),
+ * eta ~ Dir(dirichlet_alpha) over its children, after masking and renormalisation (the evaluation cache keeps the raw
+ * network rows).  The draws are Philox4x32-10 keyed by `seed` with the counter (game, ply, 0x44495249 + attempt, child rank):
+ * a step-wise search uses (root index, number of oth_search_begin calls since this call: 0 for the first) as (game, ply);
+ * a lock-step run its (game id, ply) under this seed; a stream its (game id, ply) under the STREAM's seed, like the action
+ * draws -- so a rescue replay and a snapshot / restore see the same noise.  Takes effect only with OTH_SEARCH_ALPHAZERO
+ * and dirichlet_epsilon > 0, dirichlet_alpha > 0; under OTH_SEARCH_REFERENCE it is accepted and does nothing. */
+int oth_engine_set_root_noise(oth_engine *e, int32_t enable, uint64_t seed);
 
 /* ---- step-wise search over n <= max_games root positions (BatchMCTS.search_batch semantics:
  *      one leaf per game per simulation step).  An external evaluator can be driven through
@@ -258,9 +284,11 @@ int oth_search_results(oth_engine *e, double temperature, float *pi, int32_t *vi
 
 /* ---- self-play -------------------------------------------------------------------------------
  * Plays num_games complete games on the device, max_games at a time with finished slots refilled,
- * sampling actions with a counter-based RNG keyed by (seed, game id, ply).  add_noise is accepted
- * for interface parity; Dirichlet noise on root priors cannot change any output of this search
- * (the root is never backed up, so its exploration term is zero: SURVEY L10/L12).
+ * sampling actions with a counter-based RNG keyed by (seed, game id, ply).  add_noise: under
+ * OTH_SEARCH_REFERENCE it is accepted for interface parity and does nothing -- Dirichlet noise on root priors cannot
+ * change any output of that search (the root is never backed up, so its exploration term is zero: SURVEY L10/L12);
+ * under OTH_SEARCH_ALPHAZERO (and dirichlet_epsilon > 0) every root's priors are mixed with noise drawn on the device,
+ * keyed by (seed, game id, ply, child) like the action draws (see oth_engine_set_root_noise).
  * Synchronous.  Results stay in the engine until the next run; read them with oth_selfplay_fetch. */
 int oth_selfplay_run(oth_engine *e, int32_t num_games, uint64_t seed, int32_t add_noise, int64_t *n_samples /*HOST*/,
                      void *stream);

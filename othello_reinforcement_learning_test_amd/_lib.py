@@ -64,6 +64,25 @@ def rules_name(rules):
     return "othello" if rules_id(rules) == OTH_RULES_OTHELLO else "reference"
 
 
+# search semantics (OTH_SEARCH_* of the header): "reference" = the reference's search bit for bit, the default everywhere;
+# "alphazero" = child values from the chooser's view, a counted root, observable root noise and z from the mover's view
+OTH_SEARCH_REFERENCE, OTH_SEARCH_ALPHAZERO = 0, 1
+SEARCHES = {"reference": OTH_SEARCH_REFERENCE, "alphazero": OTH_SEARCH_ALPHAZERO}
+
+
+def search_id(search):
+    """"reference" / "alphazero" (or 0 / 1) -> the OTH_SEARCH_* value; anything else is a ValueError."""
+    if isinstance(search, str) and search in SEARCHES:
+        return SEARCHES[search]
+    if not isinstance(search, (str, bool)) and search in (OTH_SEARCH_REFERENCE, OTH_SEARCH_ALPHAZERO):
+        return int(search)
+    raise ValueError("search must be one of %s, got %r" % (sorted(SEARCHES), search))
+
+
+def search_name(search):
+    return "alphazero" if search_id(search) == OTH_SEARCH_ALPHAZERO else "reference"
+
+
 def common_rules(boards, expected=None):
     """The one rule set of a list of board objects (their class attribute ``rules``; objects without one play the
     reference's game).  A mix -- among the boards, or with `expected` -- is refused with a ValueError."""
@@ -92,7 +111,7 @@ class EngineCfg(C.Structure):  # oth_engine_cfg
                 ("temperature_threshold", C.c_int32), ("c_puct", C.c_float),
                 ("dirichlet_alpha", C.c_double), ("dirichlet_epsilon", C.c_double),
                 ("store_late_onehot", C.c_int32), ("eval_cache_log2", C.c_int32), ("board_size", C.c_int32),
-                ("rules", C.c_int32)]
+                ("rules", C.c_int32), ("search", C.c_int32)]
 
 
 u64p, f32p, i32p, f64p, i64p = (C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
@@ -152,6 +171,7 @@ _SIGS = {
     "oth_engine_create": (vp, [C.POINTER(EngineCfg)]),
     "oth_engine_destroy": (None, [vp]),
     "oth_engine_set_net": (C.c_int, [vp, vp]),
+    "oth_engine_set_root_noise": (C.c_int, [vp, C.c_int32, C.c_uint64]),
     "oth_search_begin": (C.c_int, [vp, u64p, u64p, C.c_int32, vp]),
     "oth_search_select": (C.c_int, [vp, vp]),
     "oth_search_leaves": (C.c_int, [vp, i32p, u64p, u64p, u64p, vp]),

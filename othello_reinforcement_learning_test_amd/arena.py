@@ -16,8 +16,22 @@ import time
 from dataclasses import dataclass
 from typing import List
 
+from . import _lib
 from .bitboard import OthelloBitboard
 from .mcts import MCTS, best_action_from_policy
+
+
+def _check_search(search, *searchers):
+    """`search` (None = whatever the players were built with) against the semantics of every searching object given
+    (an MCTSPlayer, a BatchMCTS; host-side players have none): a mismatch is a ValueError, like a mix of rule sets."""
+    if search is None:
+        return None
+    want = _lib.search_name(search)
+    for p in searchers:
+        got = getattr(p, "search", None)
+        if isinstance(got, str) and got != want:
+            raise ValueError("search=%r, but %s searches under %r" % (want, getattr(p, "name", type(p).__name__), got))
+    return want
 
 
 class Player:
@@ -71,23 +85,24 @@ class GreedyPlayer(Player):
 class MCTSPlayer(Player):
     """players.py:115-157 on the HIP search (c_puct 1.0, temperature 0)."""
 
-    def __init__(self, model, device=None, num_simulations=50, name="MCTS-AI", precision=None):
+    def __init__(self, model, device=None, num_simulations=50, name="MCTS-AI", precision=None, search="reference"):
         super().__init__(name)
         self.model = model
         self.device = device
         self.num_simulations = num_simulations
-        self.mcts = MCTS(model=model, device=device, c_puct=1.0, precision=precision)
+        self.search = _lib.search_name(search)   # "alphazero": the player maximises its OWN value (DESIGN section 1)
+        self.mcts = MCTS(model=model, device=device, c_puct=1.0, precision=precision, search=self.search)
 
     def get_action(self, board):
         return self.mcts.get_best_action(board, num_simulations=self.num_simulations)
 
     @classmethod
-    def from_checkpoint(cls, checkpoint_path, device=None, num_simulations=50):
+    def from_checkpoint(cls, checkpoint_path, device=None, num_simulations=50, search="reference"):
         """players.py:159-211 (architecture inferred from the key names; loaded with weights_only=True)."""
         from .replay import load_checkpoint_model
         model = load_checkpoint_model(checkpoint_path)
         return cls(model=model, device=device, num_simulations=num_simulations,
-                   name="MCTS-AI-%dsim" % num_simulations)
+                   name="MCTS-AI-%dsim" % num_simulations, search=search)
 
 
 @dataclass
@@ -129,11 +144,14 @@ def _result_from_final_board(board, p1_name, p2_name, starting_player, duration)
 class Arena:
     """arena.py:55-232"""
 
-    def __init__(self, verbose=True, board_class=OthelloBitboard):
+    def __init__(self, verbose=True, board_class=OthelloBitboard, search=None):
         self.verbose = verbose
         self.board_class = board_class   # StandardOthelloBitboard: the matches are standard Othello (MCTSPlayer follows the board)
+        # the search semantics the searching players of a match must have been built with (None: not checked)
+        self.search = None if search is None else _lib.search_name(search)
 
     def play_game(self, player1, player2, starting_player=1):
+        _check_search(self.search, player1, player2)
         board = self.board_class()
         board.reset()
         player1.reset()
@@ -198,7 +216,8 @@ class BatchedArena:
     on the host game by game, in game order (so a seeded RandomPlayer consumes python's RNG deterministically).
     For deterministic opponents the results equal ``Arena.play_matches`` game for game."""
 
-    def __init__(self, batch_mcts, num_simulations=50, board_class=OthelloBitboard):
+    def __init__(self, batch_mcts, num_simulations=50, board_class=OthelloBitboard, search=None):
+        self.search = _check_search(search, batch_mcts) or getattr(batch_mcts, "search", "reference")
         self.batch_mcts = batch_mcts          # parallel_self_play.BatchMCTS
         self.num_simulations = num_simulations
         self.board_class = board_class        # the searches follow the boards' rule set

@@ -16,6 +16,11 @@
 //
 // Reference semantics reproduced: L8 expand, L9 select, L10 backup incl. the root
 // never being backed up, L11 terminal leaves, L13 policy from visit counts, L14-L18 worker loops.
+//
+// Search semantics are a compile-time parameter S of the tree kernels (cfg.search): kSearchReference, the default of every
+// template below, is all of the above bit for bit; kSearchAlphaZero inverts the backup sign (an edge holds the value from
+// the view of the side that chose it), counts the root's simulations in its exploration term, mixes Dirichlet noise into
+// the root priors on request and writes z from the view of the side to move at each ply.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -51,6 +56,23 @@ enum : int { TREE_NONE = 0, TREE_SELECT = 1, TREE_PLY = 2 };       // what k_tre
 enum : int { ST_ACTIVE = 0, ST_DONE = 1, ST_FLAGS = 2, ST_NEXT = 3 };  // words of Dev::status
 enum : int32_t { FLAG_HIST_OVERFLOW = 1 };
 constexpr int kCachedSlot = -2;  // eval_slot value: the result row is in Dev::cres[g] (evaluation-cache hit)
+
+constexpr int kSearchReference = 0;  // the reference's search: the default, parity-pinned
+constexpr int kSearchAlphaZero = 1;  // chooser's-view backup, counted root, root noise, mover's-view z
+constexpr bool search_ok(int s) { return s == kSearchReference || s == kSearchAlphaZero; }
+
+// Root Dirichlet noise of a launch (kSearchAlphaZero only).  A trailing kernel argument of its own, not a part of Dev: the
+// kernels' other arguments keep their offsets, and an instantiation that never reads it is unchanged.
+struct RootNoise {
+    double alpha, eps;   // cfg.dirichlet_alpha, cfg.dirichlet_epsilon
+    uint64_t seed;       // Philox key
+    int32_t on;          // 0: the root priors stay as the evaluator gave them
+    int32_t standalone;  // 1: step-wise search, counter (slot, count); 0: self-play, counter (game id, ply)
+    uint32_t count;      // oth_search_begin calls since oth_engine_set_root_noise
+    uint32_t pad_;
+    double* eta;         // [n_slots][64]: the Dirichlet draw of each queued root, lane = square (a pass root: lane 0);
+                         // written by k_root_noise when the root is queued, read by the root's expansion
+};
 
 struct Dev {  // device pointers + scalars handed to every kernel by value
     int32_t n_slots, cap_nodes, cap_edges, cap_path, num_sims, temp_threshold, store_late_onehot;
@@ -101,14 +123,33 @@ struct Dev {  // device pointers + scalars handed to every kernel by value
 __device__ __forceinline__ double wave_max_f64(double v) { return bfly_max_f64(v); }
 __device__ __forceinline__ int wave_sum_i32(int v) { return bfly_sum_i32(v); }
 __device__ __forceinline__ int wave_max_i32(int v) { return bfly_max_i32(v); }
+// float64 sum over the wave on the same butterfly (wave_bfly.h's bfly_pair, both halves of the double per step); kept here
+// because only the root noise uses it
+template <int OFF>
+__device__ __forceinline__ double bfly_add_f64(double v) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    uint32_t xl, yl, xh, yh;
+    bfly_pair<OFF>((uint32_t)b, xl, yl);
+    bfly_pair<OFF>((uint32_t)(b >> 32), xh, yh);
+    return __longlong_as_double((long long)(((uint64_t)xh << 32) | xl)) +
+           __longlong_as_double((long long)(((uint64_t)yh << 32) | yl));
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v = bfly_add_f64<32>(v); v = bfly_add_f64<16>(v); v = bfly_add_f64<8>(v);
+    v = bfly_add_f64<4>(v); v = bfly_add_f64<2>(v); v = bfly_add_f64<1>(v);
+    return v;
+}
 
 // mcts.py:152-168 / parallel_self_play.py:199-204: child.update(v); v = -v from the leaf upwards.
 // Edges on a path are distinct, so lane i updates path entry i (sign by distance from the leaf).
 // link_child != 0: the leaf edge (path[depth-1]) additionally gets its new child node id, in the same
 // read-modify-write (no second store to that edge from another lane).
-template <typename PathT>
+// S = kSearchAlphaZero: the sign is inverted -- `value` is from the view of the side to move AT the leaf, the leaf edge was
+// chosen by the other side and gets -value, its parent's edge +value, and so on upwards.
+template <int S = kSearchReference, typename PathT>
 __device__ __forceinline__ void backup_path(Edge* edges, const PathT* path, int depth, double value, int lane,
                                             int link_child) {
+    if constexpr (S == kSearchAlphaZero) value = -value;
     for (int i = lane; i < depth; i += 64) {
         Edge* e = &edges[path[i]];
         const double v = ((depth - 1 - i) & 1) ? -value : value;
@@ -194,13 +235,103 @@ __device__ __forceinline__ void write_eval(const Dev& d, int slot, uint64_t sb, 
     }
 }
 
+// ---- counter-based random numbers ------------------------------------------------------------------
+// Philox4x32-10 keyed by (seed) over the counter (c0, c1, c2, c3): two uniform doubles in [0,1), each of 53 random bits by
+// the construction numpy's random_sample uses, (a>>5, b>>6), from the words (x0, x1) and (x2, x3)
+__device__ inline void philox4x32(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, double& ua, double& ub) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = c3;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1;
+        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
+        x0 = y0; x1 = y1; x2 = y2; x3 = y3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    ua = ((double)(x0 >> 5) * 67108864.0 + (double)(x1 >> 6)) / 9007199254740992.0;
+    ub = ((double)(x2 >> 5) * 67108864.0 + (double)(x3 >> 6)) / 9007199254740992.0;
+}
+// The action draw: the same generator at counter (game id, ply, 0x2545F491, 0x9E3779B9), first double only (restated in
+// oracle/othello_oracle.c orc_philox_uniform; the two are compared bit for bit).  Kept as its own text, not as a call of
+// philox4x32: through the call the ply step's instructions came out in another order, and the default instantiations are
+// held to the instructions they had before the generator was generalised.
+__device__ inline double philox_uniform(uint64_t seed, uint32_t c0, uint32_t c1) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t x0 = c0, x1 = c1, x2 = 0x2545F491u, x3 = 0x9E3779B9u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1;
+        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
+        x0 = y0; x1 = y1; x2 = y2; x3 = y3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    // 53 random bits, the construction numpy's random_sample uses: (a>>5, b>>6)
+    return ((double)(x0 >> 5) * 67108864.0 + (double)(x1 >> 6)) / 9007199254740992.0;
+}
+
+// One Gamma(alpha, 1) variate for child `rank` of the root keyed by (seed, c0, c1): Marsaglia-Tsang in float64.  Attempt t
+// draws (u1, u2) from counter (c0, c1, 0x44495249 + 2t, rank) and (u3, u4) from (c0, c1, 0x44495249 + 2t + 1, rank); the
+// words differ from the action draw's (rank <= 59).  alpha < 1 is drawn as Gamma(alpha + 1) * U^(1/alpha).  64 rejections
+// in a row give d (unreachable in practice: it only bounds the loop).
+constexpr uint32_t kNoiseWord = 0x44495249u;
+__device__ inline double gamma_draw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t rank, double alpha) {
+    const double a = alpha < 1.0 ? alpha + 1.0 : alpha;
+    const double dd = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * dd);
+    for (uint32_t t = 0; t < 64; ++t) {
+        double u1, u2, u3, u4;
+        philox4x32(seed, c0, c1, kNoiseWord + 2 * t, rank, u1, u2);
+        philox4x32(seed, c0, c1, kNoiseWord + 2 * t + 1, rank, u3, u4);
+        const double x = sqrt(-2.0 * log(1.0 - u1)) * cos(2.0 * M_PI * u2);
+        const double w = 1.0 + c * x;
+        const double v = w * w * w;
+        if (v <= 0.0) continue;
+        if (log(u3) < x * x / 2.0 + dd - dd * v + dd * log(v)) {
+            double gv = dd * v;
+            if (alpha < 1.0) gv *= exp(log(1.0 - u4) / alpha);
+            return gv;
+        }
+    }
+    return dd;
+}
+
+// eta ~ Dir(alpha) over the children of every root queued by the launch before (pend == PEND_ROOT: k_search_begin, or the
+// ply step of k_tree): one wave per slot, one lane per child (lane = square; the single child of a pass root: lane 0), the
+// gamma variates normalised by a float64 butterfly sum.  A kernel of its own, launched only while the noise is on: inlined
+// into the expansion, the float64 log / cos / exp took k_tree from 73 to 119 VGPRs and into spills.  The expansion of the
+// root (expand_pending) reads its lane's eta.  Keyed by (seed; slot, count) for a step-wise search and by (seed; game id, ply)
+// in self-play, so a replay of the same root draws the same noise.
+// (It takes the few per-slot arrays it reads, not the whole of Dev.  Two scalar registers still spill into vector lanes, no
+// memory: cos()'s argument reduction)
+__global__ __launch_bounds__(256) void k_root_noise(const int32_t* __restrict__ pend, const uint64_t* __restrict__ leaf_legal,
+                                                    const int32_t* __restrict__ g_id, const int32_t* __restrict__ g_ply,
+                                                    int n_slots, RootNoise nz) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= n_slots || pend[g] != PEND_ROOT) return;   // (wave-uniform)
+    const uint64_t legal = leaf_legal[g];
+    const bool pass = legal == 0;
+    const bool has = pass ? (lane == 0) : ((legal >> lane) & 1ULL);
+    const int rank = __popcll(legal & ((1ULL << lane) - 1ULL));
+    const int nch = pass ? 1 : __popcll(legal);
+    const uint32_t c0 = nz.standalone ? (uint32_t)g : (uint32_t)g_id[g];
+    const uint32_t c1 = nz.standalone ? nz.count : (uint32_t)g_ply[g];
+    const double gv = has ? gamma_draw(nz.seed, c0, c1, (uint32_t)rank, nz.alpha) : 0.0;
+    const double tot = wave_sum_f64(gv);
+    const double eta = (tot > 0.0 && tot < INFINITY) ? gv / tot : 1.0 / (double)nch;
+    nz.eta[(size_t)g * 64 + lane] = has ? eta : 0.0;
+}
+
 // ---- expand + backup (node.py:62-89, mcts.py:133-148) ---------------------------------------------
 // The pending position of game g (its root, or the leaf chosen by the previous launch) has been evaluated:
 // mask + renormalise the priors, append the node and its edges, link it and back the value up.
-template <int BS>
+// S = kSearchAlphaZero: a ROOT's priors are mixed with Dirichlet noise when the launch asks for it (nz.on), after the
+// masking and renormalisation (so the evaluation cache, which holds raw network rows, is upstream of the noise).
+template <int BS, int S = kSearchReference>
 __device__ __forceinline__ void expand_pending(const Dev& d, int g, int lane, int pend,
                                                const float* __restrict__ policy, const float* __restrict__ value,
-                                               int is_log) {
+                                               int is_log, const RootNoise& nz = RootNoise{}) {
     constexpr int CELLS = Geo<BS>::CELLS, NP = Geo<BS>::NPOL;
     const int slot = d.eval_slot[g];
     const float* pol = slot >= 0 ? policy + (size_t)slot * NP : d.cres + (size_t)g * 66;
@@ -231,6 +362,12 @@ __device__ __forceinline__ void expand_pending(const Dev& d, int g, int lane, in
     float prior;
     if (sum > 0.0f) prior = (pass ? m64 : m) / sum;                  // masked_probs /= prob_sum
     else prior = (float)(1.0 / (double)nch);                         // node.py:78-80 uniform fallback
+    if constexpr (S == kSearchAlphaZero) {
+        // P' = (float)((1 - eps) * P + eps * eta): eta of this root was drawn when it was queued (k_root_noise), lane =
+        // square, lane 0 for the pass; a pass root has eta = 1 and keeps its prior
+        if (pend == PEND_ROOT && nz.on)
+            prior = (float)((1.0 - nz.eps) * (double)prior + nz.eps * nz.eta[(size_t)g * 64 + lane]);
+    }
     Node* nodes = d.nodes + (size_t)g * d.cap_nodes;
     Edge* edges = d.edges + (size_t)g * d.cap_edges;
     const int id = d.n_nodes[g], base = d.n_edges[g];
@@ -253,7 +390,7 @@ __device__ __forceinline__ void expand_pending(const Dev& d, int g, int lane, in
     }
     if (depth > 0) {
         const double v = (double)(slot >= 0 ? value[slot] : pol[65]);  // values[j].item(): float32 -> python float (cache rows: [65])
-        backup_path(edges, path, depth, v, lane, id);
+        backup_path<S>(edges, path, depth, v, lane, id);
     }
 }
 
@@ -323,23 +460,6 @@ __global__ __launch_bounds__(256) void k_cache_insert(Dev d, const float* __rest
     }
 }
 
-// Philox4x32-10 keyed by (seed), counter (game id, ply, 0x2545F491, 0x9E3779B9): one uniform double in [0,1)
-// per decision (restated in oracle/othello_oracle.c orc_philox_uniform; the two are compared bit for bit)
-__device__ inline double philox_uniform(uint64_t seed, uint32_t c0, uint32_t c1) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    uint32_t x0 = c0, x1 = c1, x2 = 0x2545F491u, x3 = 0x9E3779B9u;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
-        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1;
-        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
-        x0 = y0; x1 = y1; x2 = y2; x3 = y3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // 53 random bits, the construction numpy's random_sample uses: (a>>5, b>>6)
-    return ((double)(x0 >> 5) * 67108864.0 + (double)(x1 >> 6)) / 9007199254740992.0;
-}
-
 // (re)start the search of slot g from position (sb, ob): empty tree, root written to batch slot `slot`
 __device__ __forceinline__ void begin_root(const Dev& d, int g, uint64_t sb, uint64_t ob, uint64_t lg, int slot,
                                            int lane) {
@@ -397,9 +517,11 @@ __global__ void k_slots_init(Dev d, int n_start, int stagger) {
 //                       has come start their first game;
 //          TREE_NONE    nothing (last launch of a stand-alone search).
 // R = rule set (othello_rules.h): only the post-shift masks inside the rules calls differ between the instantiations.
-template <int MODE, int BS, int R>
+// S = search semantics (top of this file): the backup sign, the root's parent count in the descent and the root noise of the
+// expansion differ; `nz` is read by the kSearchAlphaZero instantiations only.
+template <int MODE, int BS, int R, int S = kSearchReference>
 __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ policy, const float* __restrict__ value,
-                                              int is_log, const int32_t* __restrict__ forced, int refill) {
+                                              int is_log, const int32_t* __restrict__ forced, int refill, RootNoise nz) {
     constexpr int CELLS = Geo<BS>::CELLS;
     extern __shared__ uint32_t lds_path_all[];  // [4 waves][cap_path]: the path of the current descent
     __shared__ BlockTally bt;
@@ -409,7 +531,11 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
     const bool in_range = g < d.n_slots;
     {
         const int pend = in_range ? d.pend[g] : PEND_NONE;
-        if (pend != PEND_NONE) expand_pending<BS>(d, g, lane, pend, policy, value, is_log);
+        if constexpr (S == kSearchReference) {
+            if (pend != PEND_NONE) expand_pending<BS>(d, g, lane, pend, policy, value, is_log);
+        } else {
+            if (pend != PEND_NONE) expand_pending<BS, S>(d, g, lane, pend, policy, value, is_log, nz);
+        }
     }
     if constexpr (MODE == TREE_NONE) return;
     // the descent / the ply step below read nodes and edges other lanes of this wave have just written
@@ -438,14 +564,31 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                 const int ei = (int)nd.edge_base + rank;
                 double score = -INFINITY;
                 int e_n = 0, e_child = 0;
-                if (act) {
-                    const Edge e = edges[ei];
+                if constexpr (S == kSearchReference) {
+                    if (act) {
+                        const Edge e = edges[ei];
+                        e_n = e.n;
+                        e_child = e.child;
+                        const double q = e.n == 0 ? 0.0 : e.w / (double)e.n;          // node.py:51-60
+                        const float cp_p = d.c_puct * e.prior;                       // float32 product (weak python scalar)
+                        const double u = (double)cp_p * d.sqrt_tab[pv] / (double)(1 + e.n);  // node.py:116
+                        score = q + u;                                               // node.py:119
+                    }
+                } else {
+                    // the same arithmetic with a counted root: its parent count is 1 + the simulations backed up so far
+                    // (= 1 + the visits of its children), what every interior node already sees (its own expansion visit
+                    // plus the visits through it); sqrt_tab reaches num_sims + 1
+                    Edge e{0.0, 0.0f, 0, 0};
+                    if (act) e = edges[ei];
                     e_n = e.n;
                     e_child = e.child;
-                    const double q = e.n == 0 ? 0.0 : e.w / (double)e.n;          // node.py:51-60
-                    const float cp_p = d.c_puct * e.prior;                       // float32 product (weak python scalar)
-                    const double u = (double)cp_p * d.sqrt_tab[pv] / (double)(1 + e.n);  // node.py:116
-                    score = q + u;                                               // node.py:119
+                    if (node == 0) pv = 1 + wave_sum_i32(e_n);
+                    if (act) {
+                        const double q = e.n == 0 ? 0.0 : e.w / (double)e.n;
+                        const float cp_p = d.c_puct * e.prior;
+                        const double u = (double)cp_p * d.sqrt_tab[pv] / (double)(1 + e.n);
+                        score = q + u;
+                    }
                 }
                 const double best = wave_max_f64(score);
                 const unsigned long long eq = __ballot(act && score == best);
@@ -468,7 +611,7 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
         if (!live) return;
         if (cached) slot = kCachedSlot;
         if (terminal) {  // parallel_self_play.py:133-135: back up float(get_winner()) immediately
-            backup_path(edges, lpath, depth, (double)winner(sb, ob), lane, 0);
+            backup_path<S>(edges, lpath, depth, (double)winner(sb, ob), lane, 0);
             if (lane == 0) d.pend[g] = PEND_NONE;
         } else {
             if (slot >= 0) write_eval(d, slot, sb, ob, lg, lane);
@@ -664,7 +807,8 @@ __global__ void k_scan_lengths(const int32_t* __restrict__ len, const int32_t* _
     }
 }
 
-template <int BS>
+// S = kSearchAlphaZero: z is the outcome from the view of the side to move at the ply (see below)
+template <int BS, int S = kSearchReference>
 __global__ __launch_bounds__(256) void k_compact(const uint64_t* __restrict__ hist_bits, const float* __restrict__ hist_pi,
                                                  const int32_t* __restrict__ len_out, const int32_t* __restrict__ win,
                                                  const int32_t* __restrict__ list, int mask,
@@ -689,8 +833,15 @@ __global__ __launch_bounds__(256) void k_compact(const uint64_t* __restrict__ hi
     }
     if (lane == 0) {
         pis[o * NP + CELLS] = hist_pi[h * 65 + CELLS];
-        const int player = (ply & 1) ? -1 : 1;           // parallel_self_play.py:385
-        zs[o] = (float)(win[hidx] * player);              // parallel_self_play.py:404
+        if constexpr (S == kSearchReference) {
+            const int player = (ply & 1) ? -1 : 1;           // parallel_self_play.py:385
+            zs[o] = (float)(win[hidx] * player);              // parallel_self_play.py:404
+        } else {
+            // win is relative to the side to move after the game's last ply; the sides alternate every ply (a pass is a
+            // ply), so that side is the mover of ply p exactly when len - p is even
+            const int player = ((len_out[gi] - ply) & 1) ? -1 : 1;
+            zs[o] = (float)(win[hidx] * player);
+        }
     }
 }
 
@@ -732,6 +883,13 @@ struct oth_engine {
     int device = 0;   // HIP device of every allocation of this engine
     int board = 8;    // board size: 8 (the reference's game) or 6
     int rules = kRulesReference;   // rule set of every rules call of this engine's kernels (cfg.rules)
+    int search = kSearchReference; // search semantics of this engine's tree kernels and of its z (cfg.search)
+    // root noise: what oth_engine_set_root_noise asked for (step-wise search, lock-step, stream) and what the launches of
+    // the current search / run carry (bound by arm_noise at its start)
+    bool rn_enable = false;
+    uint64_t rn_seed = 0;
+    uint32_t rn_begins = 0;        // oth_search_begin calls since the last set
+    RootNoise nz{};
     int cells() const { return board * board; }
     int npol() const { return board * board + 1; }
     int32_t n_roots = 0;
@@ -794,6 +952,32 @@ static inline int blocks_for(int n_slots) { return (n_slots + 3) / 4; }
             OTH_DISPATCH_BS(e, __VA_ARGS__);                          \
         }                                                             \
     } while (0)
+
+// ... and with the search semantics as a constant S on top of either: k_tree (BS, R, S) and k_compact (BS, S)
+#define OTH_DISPATCH_S(e, INNER, ...)                                 \
+    do {                                                              \
+        if ((e)->search == kSearchAlphaZero) {                        \
+            constexpr int S = kSearchAlphaZero;                       \
+            INNER(e, __VA_ARGS__);                                    \
+        } else {                                                      \
+            constexpr int S = kSearchReference;                       \
+            INNER(e, __VA_ARGS__);                                    \
+        }                                                             \
+    } while (0)
+#define OTH_DISPATCH_BSS(e, ...) OTH_DISPATCH_S(e, OTH_DISPATCH_BS, __VA_ARGS__)
+#define OTH_DISPATCH_BSRS(e, ...) OTH_DISPATCH_S(e, OTH_DISPATCH_BSR, __VA_ARGS__)
+
+// the root noise the launches of a search / run carry: on only under kSearchAlphaZero with a positive epsilon and alpha
+static void arm_noise(oth_engine* e, bool want, uint64_t seed, bool standalone, uint32_t count) {
+    RootNoise& z = e->nz;
+    z.alpha = e->cfg.dirichlet_alpha;
+    z.eps = e->cfg.dirichlet_epsilon;
+    z.seed = seed;
+    z.on = (want && e->search == kSearchAlphaZero && z.eps > 0.0 && z.alpha > 0.0) ? 1 : 0;
+    z.standalone = standalone ? 1 : 0;
+    z.count = count;
+    z.pad_ = 0;
+}
 
 template <typename T>
 static int dev_alloc(oth_engine* e, T** p, size_t count) {
@@ -896,6 +1080,14 @@ static inline void bind_cursor(oth_engine* e) {
     e->d.n_eval_next = e->n_eval2 + (e->ev_par ^ 1);
     e->ev_par ^= 1;
 }
+// Dirichlet draws for the roots the launch before has queued (nothing to do while the noise is off)
+static int launch_root_noise(oth_engine* e, hipStream_t s) {
+    if (!e->nz.on) return OTH_OK;
+    hipLaunchKernelGGL(k_root_noise, dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d.pend, e->d.leaf_legal,
+                       e->d.g_id, e->d.g_ply, e->d.n_slots, e->nz);
+    OTH_HIP(hipGetLastError());
+    return OTH_OK;
+}
 static int launch_tree(oth_engine* e, int mode, int is_log, const int32_t* forced, int refill, hipStream_t s) {
     int r = span_begin(e, s, 1);
     if (r) return r;
@@ -903,15 +1095,19 @@ static int launch_tree(oth_engine* e, int mode, int is_log, const int32_t* force
     const dim3 grid(blocks_for(e->d.n_slots)), block(256);
     const size_t lds = sizeof(uint32_t) * 4 * e->d.cap_path;
     if (mode == TREE_SELECT)
-        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS, R>), grid, block, lds, s, e->d, e->d.logp, e->d.val,
-                                              is_log, forced, refill));
+        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS, R, S>), grid, block, lds, s, e->d, e->d.logp,
+                                               e->d.val, is_log, forced, refill, e->nz));
     else if (mode == TREE_PLY)
-        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS, R>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
-                                              forced, refill));
+        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS, R, S>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
+                                               is_log, forced, refill, e->nz));
     else
-        OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS, R>), grid, block, 0, s, e->d, e->d.logp, e->d.val, is_log,
-                                              forced, refill));
+        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS, R, S>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
+                                               is_log, forced, refill, e->nz));
     OTH_HIP(hipGetLastError());
+    if (mode == TREE_PLY) {   // the ply step queued the next roots: draw their noise
+        r = launch_root_noise(e, s);
+        if (r) return r;
+    }
     return span_end(e, s);
 }
 static int cache_clear(oth_engine* e, hipStream_t s) {
@@ -1020,7 +1216,7 @@ static int harvest(oth_engine* e, int n, const int32_t* ids, int64_t* n_samples,
     }
     if (total > 0) {
         const int64_t waves = (int64_t)n * kMaxPly;
-        OTH_DISPATCH_BS(e, hipLaunchKernelGGL((k_compact<BS>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
+        OTH_DISPATCH_BSS(e, hipLaunchKernelGGL((k_compact<BS, S>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
                                               e->d.hist_bits, e->d.hist_pi, e->d_len_out, e->d.game_winner, dlist,
                                               e->d.hist_mask, e->d_off, n, e->out_states, e->out_pis, e->out_zs));
         OTH_HIP(hipGetLastError());
@@ -1112,11 +1308,18 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
         set_error("oth_engine_create: rules must be OTH_RULES_REFERENCE (0) or OTH_RULES_OTHELLO (1), got %d", (int)cfg->rules);
         return nullptr;
     }
+    if (!search_ok(cfg->search)) {
+        set_error("oth_engine_create: search must be OTH_SEARCH_REFERENCE (0) or OTH_SEARCH_ALPHAZERO (1), got %d",
+                  (int)cfg->search);
+        return nullptr;
+    }
     oth_engine* e = new oth_engine();
     e->device = current_device();
     e->cfg = *cfg;
     e->board = cfg->board_size == 6 ? 6 : 8;
     e->rules = cfg->rules;
+    e->search = cfg->search;
+    arm_noise(e, false, 0, false, 0);
     Dev& d = e->d;
     const int G = cfg->max_games, S = cfg->num_simulations;
     d.n_slots = G;
@@ -1164,6 +1367,7 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
             if (hipMemset(d.ck, 0xFF, C * 2 * sizeof(uint64_t)) != hipSuccess) r = 1;
         }
     }
+    if (e->search == kSearchAlphaZero) r |= dev_alloc(e, &e->nz.eta, (size_t)G * 64);   // root noise draws, one row per slot
     double* st = nullptr;
     r |= dev_alloc(e, &st, (size_t)S + 4);
     if (!r && hipHostMalloc((void**)&e->h_status, sizeof(int32_t) * 8) != hipSuccess) r = 1;
@@ -1209,6 +1413,15 @@ int oth_engine_set_net(oth_engine* e, oth_net* net) {
     return OTH_OK;
 }
 
+int oth_engine_set_root_noise(oth_engine* e, int32_t enable, uint64_t seed) {
+    OTH_CHECK(e, "oth_engine_set_root_noise: null engine");
+    // (a stream or a lock-step run in progress keeps the noise it was begun with: e->nz is bound at a begin)
+    e->rn_enable = enable != 0;
+    e->rn_seed = seed;
+    e->rn_begins = 0;
+    return OTH_OK;
+}
+
 // ---- step-wise search ----------------------------------------------------------------------------
 int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int32_t n, void* stream) {
     OTH_NEED_DEVICE();
@@ -1216,6 +1429,7 @@ int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int3
     OTH_BIND(e->device);
     hipStream_t s = as_stream(stream);
     e->streaming = e->lockstep = false;
+    arm_noise(e, e->rn_enable, e->rn_seed, true, e->rn_begins++);
     // the roots are uploaded straight into the game-position arrays; k_search_begin reads them there
     OTH_HIP(hipMemcpyAsync(e->d.g_self, sb, sizeof(uint64_t) * n, hipMemcpyDefault, s));
     OTH_HIP(hipMemcpyAsync(e->d.g_opp, ob, sizeof(uint64_t) * n, hipMemcpyDefault, s));
@@ -1229,6 +1443,7 @@ int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int3
     OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_search_begin<BS, R>), dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d,
                                           e->d.g_self, e->d.g_opp, n));
     OTH_HIP(hipGetLastError());
+    if ((rc = launch_root_noise(e, s))) return rc;
     e->n_roots = n;
     return OTH_OK;
 }
@@ -1318,11 +1533,11 @@ int oth_search_results(oth_engine* e, double temperature, float* pi, int32_t* vi
 int oth_selfplay_run(oth_engine* e, int32_t num_games, uint64_t seed, int32_t add_noise, int64_t* n_samples,
                      void* stream) {
     OTH_NEED_DEVICE();
-    (void)add_noise;  // no observable effect on this search: see the header comment
     OTH_CHECK(e && num_games >= 1, "oth_selfplay_run: bad arguments");
     OTH_BIND(e->device);
     OTH_CHECK(e->net, "oth_selfplay_run: no network set");
     hipStream_t s = as_stream(stream);
+    arm_noise(e, add_noise != 0, seed, false, 0);  // (no effect under the reference's search: see the header comment)
     const int G = e->d.n_slots;
     const int n_start = num_games < G ? num_games : G;
     int r = reset_run(e, num_games, num_games, n_start, 0, seed, s);
@@ -1361,6 +1576,7 @@ int oth_selfplay_begin(oth_engine* e, int32_t n, void* stream) {
     OTH_CHECK(e && n >= 1 && n <= e->d.n_slots, "oth_selfplay_begin: need 1 <= n <= max_games");
     OTH_BIND(e->device);
     hipStream_t s = as_stream(stream);
+    arm_noise(e, e->rn_enable, e->rn_seed, false, 0);
     int r = reset_run(e, n, n, n, 0, 0, s);
     if (r) return r;
     e->lockstep = true;
@@ -1431,6 +1647,7 @@ int oth_stream_begin(oth_engine* e, uint64_t seed, int32_t stagger_rounds, int32
     const int G = e->d.n_slots;
     const int64_t want = hist_games > 0 ? hist_games : (int64_t)8 * G;
     OTH_CHECK(want >= 2 * (int64_t)G && want <= (1 << 24), "oth_stream_begin: hist_games must be in [2*max_games, 2^24]");
+    arm_noise(e, e->rn_enable, seed, false, 0);   // keyed like the action draws: the stream's seed, (game id, ply)
     int r = reset_run(e, (int)want, INT_MAX, G, stagger_rounds, seed, s);
     if (r) return r;
     e->streaming = true;

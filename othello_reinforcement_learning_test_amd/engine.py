@@ -467,9 +467,14 @@ class SearchEngine:
 
     def __init__(self, max_games, num_simulations, temperature_threshold=15, c_puct=1.0,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, store_late_onehot=False, evaluator=None,
-                 eval_cache_log2=0, board_size=None, rules="reference"):
-        _lib.require_device()
+                 eval_cache_log2=0, board_size=None, rules="reference", search="reference"):
+        # (both names are checked before any device call: an unknown one is a ValueError with or without a GPU)
         self.rules = _lib.rules_name(rules)   # "reference" (the default: the reference's game) or "othello" (standard)
+        # "reference" (the default: the reference's search, SURVEY 8.1 L9-L16 included) or "alphazero": child values from the
+        # view of the side that chose the move, a root that counts its simulations, root Dirichlet noise, z from the mover's view
+        self.search = _lib.search_name(search)
+        _lib.require_device()
+        self._noise = (False, 0)
         self.max_games = int(max_games)
         self.num_simulations = int(num_simulations)
         if board_size is None:   # follow the evaluator's network; 8 (the reference's game) otherwise
@@ -480,7 +485,7 @@ class SearchEngine:
         cfg = _lib.EngineCfg(self.max_games, self.num_simulations, int(temperature_threshold),
                              float(c_puct), float(dirichlet_alpha), float(dirichlet_epsilon),
                              1 if store_late_onehot else 0, int(eval_cache_log2), self.board_size,
-                             _lib.rules_id(rules))
+                             _lib.rules_id(rules), _lib.search_id(search))
         self._h = _lib.load().oth_engine_create(C.byref(cfg))
         if not self._h:
             raise _lib.OthelloHipError("oth_engine_create: " + _lib.last_error())
@@ -491,6 +496,15 @@ class SearchEngine:
     def set_evaluator(self, evaluator):
         self.evaluator = evaluator
         _lib.call("oth_engine_set_net", self._h, evaluator.handle)
+
+    def set_root_noise(self, enable, seed=0):
+        """Root Dirichlet noise (dirichlet_alpha, dirichlet_epsilon of the constructor) for the step-wise search, the
+        lock-step run and the stream begun AFTER this call; drawn on the device from a counter-based stream keyed by
+        `seed` (a stream: by its own seed), so the same seed gives the same noise.  Only search="alphazero" has a root
+        that can see it: under "reference" the call is accepted and changes nothing.  (selfplay_run takes its own
+        add_noise flag and keys the draws on the run's seed.)"""
+        self._noise = (bool(enable), int(seed) & (2**64 - 1))
+        _lib.call("oth_engine_set_root_noise", self._h, 1 if enable else 0, C.c_uint64(self._noise[1]))
 
     # ---- step-wise search ------------------------------------------------------------------
     def search_begin(self, self_b, opp_b):
@@ -541,9 +555,20 @@ class SearchEngine:
                   _lib.np_ptr(prior, C.c_float), _lib.current_stream())
         return pi, visits, wsum, prior
 
-    def search_with(self, self_b, opp_b, eval_fn, temperature=1.0):
+    @staticmethod
+    def root_values(visits, value_sum):
+        """Root value of each searched position under search="alphazero": sum of the children's W over the sum of their
+        N, in float64 (the children hold the value from the root mover's view); 0.0 where no simulation was backed up."""
+        n = np.asarray(visits, dtype=np.int64).sum(axis=-1)
+        w = np.asarray(value_sum, dtype=np.float64).sum(axis=-1)
+        return np.where(n > 0, w / np.maximum(n, 1), 0.0)
+
+    def search_with(self, self_b, opp_b, eval_fn, temperature=1.0, root_noise=False, noise_seed=0):
         """Whole search with an external evaluator: eval_fn(self u64[m], opp u64[m], legal u64[m])
-        -> (probs f32[m,65], values f32[m]).  Mirrors BatchMCTS.search_batch."""
+        -> (probs f32[m,65], values f32[m]).  Mirrors BatchMCTS.search_batch.  root_noise / noise_seed: seeded root
+        Dirichlet noise for this search (set_root_noise before its begin: root i draws at counter (i, 0))."""
+        if root_noise or self._noise[0]:
+            self.set_root_noise(root_noise, noise_seed)
         self.search_begin(self_b, opp_b)
         s, o, lg = self.search_leaves()
         p, v = eval_fn(s, o, lg)
@@ -592,11 +617,15 @@ class SearchEngine:
         return ev is not None and getattr(ev, "precision", "f32") != "f32" and hasattr(ev, "needs_rescue")
 
     def search_run_rescued(self):
-        """search_run from the roots of the last search_begin, repeated while a launch saturated."""
+        """search_run from the roots of the last search_begin, repeated while a launch saturated.  With root noise on, the
+        noise is set again before the replay, so a search that was the first since set_root_noise (what MCTS.search and
+        search_with do) is replayed with the same draws."""
         while True:
             self.search_run()
             if not (self._rescuable() and self.evaluator.needs_rescue()):
                 return
+            if self._noise[0]:
+                self.set_root_noise(*self._noise)
             self.search_begin(*self._roots)
 
     def selfplay_run_rescued(self, num_games, seed, add_noise=True):

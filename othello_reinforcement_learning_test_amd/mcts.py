@@ -8,6 +8,12 @@ Reference behaviours kept on purpose: the root is never backed u
 ``root_value`` is always 0.0 and Dirichlet noise cannot change the visit distribution; with
 ``add_dirichlet_noise=True`` the noise vector is still drawn from numpy's global RNG, as the
 reference does (mcts.py:221), so a seeded run consumes the same random stream.
+
+``search="alphazero"`` (opt-in) is the search an AlphaZero trainer expects: child values from the view
+of the side that chose the move, a counted root, and ``root_value`` = sum W / sum N over the root's children.
+``add_dirichlet_noise=True`` then turns the DEVICE's root noise on, keyed by one seed drawn from numpy's global RNG per
+search (``np.random.seed`` still makes a run reproducible); ``np.random.dirichlet`` is not drawn -- there is no golden
+stream to line up with under these semantics.
 """
 import numpy as np
 
@@ -36,7 +42,8 @@ def evaluations_from_stats(visits, value_sum, legal):
 
 class MCTS:
     def __init__(self, model, device=None, c_puct=1.0, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
-                 precision=None):
+                 precision=None, search="reference"):
+        self.search_semantics = _lib.search_name(search)
         self.model = model
         self.device = device
         self.c_puct = c_puct
@@ -51,19 +58,25 @@ class MCTS:
         if eng is None:
             eng = SearchEngine(max_games, num_simulations, c_puct=self.c_puct,
                                dirichlet_alpha=self.dirichlet_alpha,
-                               dirichlet_epsilon=self.dirichlet_epsilon, evaluator=self.evaluator, rules=rules)
+                               dirichlet_epsilon=self.dirichlet_epsilon, evaluator=self.evaluator, rules=rules,
+                               search=self.search_semantics)
             self._engines[key] = eng
         return eng
 
-    def _search_stats(self, board, num_simulations, temperature):
+    def _search_stats(self, board, num_simulations, temperature, add_dirichlet_noise=False):
         self.evaluator.refresh()
         eng = self._engine(num_simulations, rules=_lib.common_rules([board]))   # the board's own rule set
+        if self.search_semantics == "alphazero":   # the noise flag of the search path: one seed per search
+            eng.set_root_noise(add_dirichlet_noise, int(np.random.randint(0, 2**62)) if add_dirichlet_noise else 0)
         eng.search_begin([board.self_board], [board.opp_board])
         eng.search_run_rescued()   # (a launch that clamped an activation is run again at a lower activation scale)
         return eng.search_results(temperature)
 
     def search(self, board, num_simulations, temperature=1.0, add_dirichlet_noise=False):
         """-> (policy (65,) float32, root_value).  mcts.py:49-98."""
+        if self.search_semantics == "alphazero":
+            pi, visits, wsum, _ = self._search_stats(board, num_simulations, float(temperature), add_dirichlet_noise)
+            return pi[0].copy(), float(SearchEngine.root_values(visits, wsum)[0])
         if add_dirichlet_noise:  # mcts.py:85-86 / :220-221: consumes the RNG, cannot alter the result
             n_legal = len(board.get_legal_moves())
             np.random.dirichlet([self.dirichlet_alpha] * n_legal)

@@ -7,6 +7,11 @@ per simulation step over the dense leaf batch.
 
 Parallel-worker semantics kept: the search always runs at temperature 1 and the
 stored pi is always the visit distribution; argmax only picks the move after the threshold.
+
+``search="alphazero"`` (opt-in; YAML key ``mcts.semantics``) runs every engine of a worker under the
+AlphaZero search semantics: z is the outcome from the view of the side to move at the tuple's ply, ``add_dirichlet_noise``
+turns the device's root noise on, and the numpy-RNG mode no longer draws ``np.random.dirichlet`` (one noise seed per
+batch is drawn instead; there is no golden stream to line up with under these semantics).
 """
 import os
 import time
@@ -23,7 +28,8 @@ class BatchMCTS:
     (parallel_self_play.py:80-170)."""
 
     def __init__(self, model, device=None, c_puct=1.0, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
-                 precision=None, evaluator=None):
+                 precision=None, evaluator=None, search="reference"):
+        self.search = _lib.search_name(search)
         self.model = model
         self.device = device
         self.c_puct = c_puct
@@ -46,7 +52,8 @@ class BatchMCTS:
             eng = SearchEngine(cap, num_simulations, c_puct=self.c_puct,
                                dirichlet_alpha=self.dirichlet_alpha,
                                dirichlet_epsilon=self.dirichlet_epsilon,
-                               evaluator=None if self._external else self.evaluator, rules=rules)
+                               evaluator=None if self._external else self.evaluator, rules=rules,
+                               search=self.search)
             self._engines[key] = eng
         return eng
 
@@ -57,17 +64,24 @@ class BatchMCTS:
         rules = _lib.common_rules(boards)   # one rule set per call: a mix is a ValueError
         if not self._external:
             self.evaluator.refresh()
-        if add_dirichlet_noise:  # :111-118: one draw per board, in board order
+        az = self.search == "alphazero"
+        if add_dirichlet_noise and not az:  # :111-118: one draw per board, in board order
             for b in boards:
                 np.random.dirichlet([self.dirichlet_alpha] * len(b.get_legal_moves()))
         eng = self._engine(n, num_simulations, rules)
+        if az:   # the device draws the noise: one seed per call from numpy's global RNG, board i at counter (i, 0)
+            eng.set_root_noise(add_dirichlet_noise, int(np.random.randint(0, 2**62)) if add_dirichlet_noise else 0)
         sb, ob = [b.self_board for b in boards], [b.opp_board for b in boards]
         if self._external:
-            pi, _, _, _ = eng.search_with(sb, ob, self.evaluator.host_eval, float(temperature))
+            pi, visits, wsum, _ = eng.search_with(sb, ob, self.evaluator.host_eval, float(temperature),
+                                                  root_noise=eng._noise[0], noise_seed=eng._noise[1])
         else:
             eng.search_begin(sb, ob)
             eng.search_run_rescued()
-            pi, _, _, _ = eng.search_results(float(temperature))
+            pi, visits, wsum, _ = eng.search_results(float(temperature))
+        if az:
+            rv = SearchEngine.root_values(visits, wsum)
+            return [(pi[i].copy(), float(rv[i])) for i in range(n)]
         return [(pi[i].copy(), 0.0) for i in range(n)]  # root value is always 0.0
 
 
@@ -75,8 +89,10 @@ class ParallelSelfPlayWorker:
     def __init__(self, board_class, model, device=None, num_simulations=25, temperature_threshold=15,
                  num_parallel_games=8, c_puct=1.0, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
                  rng_mode=None, precision=None, verbose=True, eval_cache_log2=0, lanes=None, continuous=False,
-                 stagger_rounds=0, device_slots=None):
+                 stagger_rounds=0, device_slots=None, search="reference"):
         self.board_class = board_class
+        # the search semantics of every engine of this worker (its own, the lane engines, a grown engine)
+        self.search = _lib.search_name(search)
         # the rule set every engine of this worker plays (lane engines and a grown engine included) and the class of the
         # numpy-RNG mode's host mirror boards: the board class's
         self.rules = _lib.rules_name(getattr(board_class, "rules", "reference"))
@@ -88,7 +104,7 @@ class ParallelSelfPlayWorker:
             raise ValueError("rng_mode must be 'device' or 'numpy'")
         self.verbose = verbose
         self.batch_mcts = BatchMCTS(model, device, c_puct, dirichlet_alpha, dirichlet_epsilon,
-                                    precision=precision)
+                                    precision=precision, search=self.search)
         # device_slots: game slots of the engine in device-RNG mode.  The reference's num_parallel_games (8-32 in its
         # configs, parallel_self_play.py:232) is how many games share one network batch; with the counter-based RNG a
         # game's tuples depend on (seed, game id) only, so playing MORE games of a call at once changes nothing but the
@@ -98,12 +114,13 @@ class ParallelSelfPlayWorker:
         self.device_slots = None if device_slots is None else int(device_slots)
         self._engine_args = dict(temperature_threshold=temperature_threshold, c_puct=c_puct,
                                  dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                                 store_late_onehot=False, eval_cache_log2=eval_cache_log2, rules=self.rules)
+                                 store_late_onehot=False, eval_cache_log2=eval_cache_log2, rules=self.rules,
+                                 search=self.search)
         self.engine = SearchEngine(self.device_slots or num_parallel_games, num_simulations,
                                    temperature_threshold=temperature_threshold, c_puct=c_puct,
                                    dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                                    store_late_onehot=False, evaluator=self.batch_mcts.evaluator,
-                                   eval_cache_log2=eval_cache_log2, rules=self.rules)
+                                   eval_cache_log2=eval_cache_log2, rules=self.rules, search=self.search)
         # lanes > 1 (device RNG mode): the slots are split into independent groups, each an engine on its own
         # stream and host thread; their kernels overlap on the device (one group's network launches fill the
         # other's tails and tree-search phases: +4 % at 4096 slots).  Results are concatenated lane by lane.
@@ -117,7 +134,7 @@ class ParallelSelfPlayWorker:
                                                c_puct=c_puct, dirichlet_alpha=dirichlet_alpha,
                                                dirichlet_epsilon=dirichlet_epsilon, store_late_onehot=False,
                                                evaluator=self.batch_mcts.evaluator, eval_cache_log2=eval_cache_log2,
-                                               rules=self.rules)
+                                               rules=self.rules, search=self.search)
                                   for _ in range(self.lanes)]
         # continuous=True (device RNG only): the slots keep playing BETWEEN execute_episodes calls (oth_stream_*): a call
         # returns the games that finished during it -- at least num_episodes -- and leaves the others in flight, so
@@ -200,12 +217,14 @@ class ParallelSelfPlayWorker:
             self._lane_check.end(self._lane_engines)   # (the next call fetches its streams anew)
         return tuple(np.concatenate([o[j] for o in out]) for j in range(3))
 
-    def _run_stream(self, num_episodes):
-        """continuous mode, single engine: -> arrays of every game that finished during this call (>= num_episodes)."""
+    def _run_stream(self, num_episodes, add_dirichlet_noise=True):
+        """continuous mode, single engine: -> arrays of every game that finished during this call (>= num_episodes).
+        The root noise (search="alphazero") is bound when the stream begins: the first call's flag holds for the stream."""
         eng = self.engine
         self._ran = [eng]
         if not self._streaming:
             self.stream_seed = int(np.random.randint(0, 2**62))
+            eng.set_root_noise(add_dirichlet_noise)   # (keyed by the stream's seed; no effect under "reference")
             self._hist_games = max(8 * eng.max_games, 2 * int(num_episodes) + 4 * eng.max_games)
             eng.stream_begin(self.stream_seed, stagger_rounds=self.stagger_rounds, hist_games=self._hist_games)
             self._hist_games = 1 << (self._hist_games - 1).bit_length()   # the engine rounds the ring up to a power of two
@@ -236,11 +255,15 @@ class ParallelSelfPlayWorker:
             b.reset()
         finished = [False] * batch_size
         ply = [0] * batch_size
+        az = self.search == "alphazero"
+        if az:   # the device draws the noise, keyed by (seed, game, ply): one seed per batch from numpy's global RNG;
+            #      the lock-step run binds it when it begins
+            eng.set_root_noise(add_dirichlet_noise, int(np.random.randint(0, 2**62)) if add_dirichlet_noise else 0)
         eng.selfplay_begin(batch_size)
         alpha = self.batch_mcts.dirichlet_alpha
         while not all(finished):
             active = [i for i in range(batch_size) if not finished[i]]
-            if add_dirichlet_noise:  # drawn inside search_batch, board by board (:111-118)
+            if add_dirichlet_noise and not az:  # drawn inside search_batch, board by board (:111-118)
                 for i in active:
                     np.random.dirichlet([alpha] * len(boards[i].get_legal_moves()))
             pi, _ = eng.selfplay_search_rescued()
@@ -267,7 +290,7 @@ class ParallelSelfPlayWorker:
         t0 = time.time()
         if self.rng_mode == "device":
             if self.continuous:
-                states, pis, zs = self._run_stream(num_episodes)
+                states, pis, zs = self._run_stream(num_episodes, add_dirichlet_noise)
             else:
                 states, pis, zs = self._run_device(num_episodes, add_dirichlet_noise)
             data = tuples_from_arrays(states, pis, zs)
@@ -288,7 +311,7 @@ class ParallelSelfPlayWorker:
         games = len(self.last_game_ids) if (self.continuous and self.rng_mode == "device") else num_episodes
         ev = self.batch_mcts.evaluator
         # what the run's arithmetic was: the activation scale of the fp16-split trunk and every rescue so far
-        counters.update({"precision": getattr(ev, "precision", None), "act_scale": getattr(ev, "act_scale", None),
+        counters.update({"rules": self.rules, "search": self.search, "precision": getattr(ev, "precision", None), "act_scale": getattr(ev, "act_scale", None),
                          "rescues": len(getattr(ev, "rescues", ()))})
         if self._lane_check is not None and self._ran is self._lane_engines:
             counters.update(self._lane_check.report())
@@ -323,6 +346,9 @@ def create_parallel_self_play_worker(config, model, device=None, **kwargs):
     board_class = StandardOthelloBitboard if rules == "othello" else OthelloBitboard
     mcts = config.get("mcts", {})
     sp = config.get("self_play", {})
+    # `mcts.semantics` -- a key of THIS package (absent = "reference" = the reference's search): "alphazero" selects the
+    # opt-in search semantics.  A keyword argument `search` wins.
+    kwargs.setdefault("search", _lib.search_name(mcts.get("semantics", "reference")))
     # `self_play.continuous: true` -- a key of THIS package, absent from the reference's YAML files (absent = off = the
     # reference's call-by-call behaviour): the worker's slots keep playing between execute_episodes calls, so a trainer that
     # asks for 50-200 episodes per iteration (training.self_play_episodes_per_iter: 100 in configs/default_8x8.yaml, 50 in fast_8x8) is

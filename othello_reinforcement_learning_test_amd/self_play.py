@@ -13,6 +13,10 @@ Two random-number modes:
     (state, pi, z) stream (up to floating-point differences of the evaluator).
 Serial-worker semantics kept: the stored pi is the temperature-adjusted one (one-hot
 after ``temperature_threshold`` plies); z = winner_at_end * player with the reference's sign (L16).
+
+``search="alphazero"`` (default: what the ``mcts`` object was built with) switches both modes to the opt-in search
+semantics: z is the outcome from the view of the side to move at the tuple's ply, and ``add_dirichlet_noise`` turns the
+device's root noise on (the numpy mode then draws one noise seed per search, not ``np.random.dirichlet``).
 """
 import os
 from dataclasses import dataclass
@@ -47,8 +51,12 @@ def tuples_from_arrays(states, pis, zs, block=512):
 
 
 class SelfPlayWorker:
-    def __init__(self, board_class, mcts, num_simulations=25, temperature_threshold=15, rng_mode=None):
+    def __init__(self, board_class, mcts, num_simulations=25, temperature_threshold=15, rng_mode=None, search=None):
         self.board_class = board_class
+        own = getattr(mcts, "search_semantics", "reference")
+        self.search = _lib.search_name(own if search is None else search)
+        if self.search != own:   # the numpy mode searches through `mcts`, the device mode through an engine of this worker
+            raise ValueError("search=%r, but the MCTS object was built with search=%r" % (self.search, own))
         self.rules = _lib.rules_name(getattr(board_class, "rules", "reference"))   # the device engine plays the class's rules
         self.mcts = mcts
         self.num_simulations = num_simulations
@@ -78,6 +86,8 @@ class SelfPlayWorker:
             board.make_move(action)
             ply += 1
         winner = board.get_winner()
+        if self.search == "alphazero":   # winner is relative to the side to move at the end: ply `ply`
+            return [(s.state, s.policy, float(winner if (ply - t) % 2 == 0 else -winner)) for t, s in enumerate(history)]
         return [(s.state, s.policy, float(winner * s.player)) for s in history]
 
     # ---- all episodes at once on the device ------------------------------------------------
@@ -89,7 +99,7 @@ class SelfPlayWorker:
                 g, self.num_simulations, temperature_threshold=self.temperature_threshold,
                 c_puct=self.mcts.c_puct, dirichlet_alpha=self.mcts.dirichlet_alpha,
                 dirichlet_epsilon=self.mcts.dirichlet_epsilon, store_late_onehot=True,
-                evaluator=self.mcts.evaluator, rules=self.rules)
+                evaluator=self.mcts.evaluator, rules=self.rules, search=self.search)
         return self._engine
 
     def execute_episodes(self, num_episodes, add_dirichlet_noise=True):
