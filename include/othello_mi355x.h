@@ -244,6 +244,26 @@ typedef struct {
 #define OTH_SEARCH_ALPHAZERO 1
 
 oth_engine *oth_engine_create(const oth_engine_cfg *cfg);
+/* oth_engine_create with tree reuse as an option (oth_engine_cfg keeps its layout: the option is an argument).
+ * tree_reuse = 0: oth_engine_create(cfg) exactly -- every ply starts from an empty tree, today's behaviour bit for bit.
+ * tree_reuse = 1 (needs cfg->search = OTH_SEARCH_ALPHAZERO; with OTH_SEARCH_REFERENCE creation fails: the reference's
+ * contract has no reuse; any other value fails too): the subtree under the move played becomes the next ply's tree.
+ *   re-rooting: a ply step that plays action a from root r with edge(r, a).child = c != 0, the game going on, makes c node 0;
+ *     every kept edge keeps its W, prior and N bit for bit, every node not reachable from c is dropped (k_reroot, on the
+ *     device).  c == 0 (an unvisited move: possible with forced actions) queues a fresh root as without reuse; a finished game
+ *     refills as without reuse.
+ *   budget (top-up, not add-on): num_simulations = S is the number of visits the root's children hold when a search ends.
+ *     An inherited root starts with V0 = N_c - 1 <= S - 1 visits and runs S - V0 >= 1 new simulations, a fresh root S; pi is
+ *     over exactly S visits and every bound of the arena (S + 2 nodes, u16 counts) holds unchanged.  The host still launches
+ *     S select rounds per ply: a slot at its budget sits a round out (no descent, no evaluation slot).
+ *   noise: an inherited root's stored priors are un-noised (it was expanded as an interior node); with root noise on,
+ *     P' = (float)((1 - eps) * P + eps * eta) is mixed into them at the re-root, eta from the same Philox stream and counter
+ *     as a fresh root of that (game id, ply) -- step-wise: (root index, count), oth_search_advance advancing the count as
+ *     oth_search_begin does.  A root's own edges never survive the next re-root, so noise never compounds.
+ *   weights reloaded between stream steps: inherited statistics stay (a game in flight keeps what it has searched, as it
+ *     continues with the new weights); the evaluation cache is upstream of the tree and unaffected.
+ * Independent of `rules` and of the board size. */
+oth_engine *oth_engine_create_reuse(const oth_engine_cfg *cfg, int32_t tree_reuse);
 void oth_engine_destroy(oth_engine *e);
 /* evaluator used by oth_search_run / oth_selfplay_run (not owned) */
 int oth_engine_set_net(oth_engine *e, oth_net *net);
@@ -263,6 +283,14 @@ int oth_engine_set_root_noise(oth_engine *e, int32_t enable, uint64_t seed);
  *      leaves()/expand(); the built-in network through oth_search_run. -------------------------- */
 /* roots: HOST arrays self[n], opp[n].  Resets the trees and queues the n roots for evaluation. */
 int oth_search_begin(oth_engine *e, const uint64_t *self_b, const uint64_t *opp_b, int32_t n, void *stream);
+/* Tree reuse in the step-wise search (engines of oth_engine_create_reuse(cfg, 1); an error on any other): root i plays
+ * actions[i] (HOST [n], n of the last oth_search_begin).  Where the move's child has been expanded its subtree becomes the
+ * tree (visible in oth_search_results at once; root noise, when on, is mixed in by the next select / expand launch);
+ * otherwise a fresh root is queued and shows up in oth_search_leaves / oth_search_expand like a root of oth_search_begin.
+ * A root whose successor is terminal, whose action is -1 or not legal, or that is idle already goes idle: it takes no
+ * further part until the next oth_search_begin.  oth_search_select and oth_search_run then top every root up to
+ * num_simulations visits (see oth_engine_create_reuse).  oth_engine_counters keep counting from the last oth_search_begin. */
+int oth_search_advance(oth_engine *e, const int32_t *actions /*HOST [n]*/, void *stream);
 /* select one leaf per game (node.py:91 select_child, parallel_self_play.py:172 _select_leaf);
  * terminal leaves are backed up at once with float(get_winner()) (mcts.py:127-130). */
 int oth_search_select(oth_engine *e, void *stream);
@@ -334,7 +362,8 @@ int oth_selfplay_device_ptrs(oth_engine *e, float **states, float **pis, float *
 
 /* Snapshot / restore of a stream or a lock-step run BETWEEN two calls (no reference counterpart: the reference's fp32
  * network cannot saturate, parallel_self_play.py:53-78): snapshot copies the slots' game positions, the queued roots, the
- * status words, the counters and the bookkeeping of the history ring (a few MB, on `stream`) so that a step / search whose
+ * status words, the counters and the bookkeeping of the history ring (a few MB, on `stream`; with tree_reuse also the node
+ * and edge arenas, which then hold the inherited subtrees) so that a step / search whose
  * network launches saturated (oth_net_saturated) can be played again from exactly the state it started in after
  * oth_net_set_act_scale: restore puts that state back, forgets the games the abandoned call finished (their ring
  * entries are free again) and clears the evaluation cache.  Games are keyed by (seed, game id, ply), so the repeated call
@@ -345,8 +374,14 @@ int oth_engine_snapshot(oth_engine *e, void *stream);
 int oth_engine_restore(oth_engine *e, void *stream);
 
 /* counters of the last run: [0] network evaluations, [1] simulations, [2] plies, [3] games,
- * [4] network batches launched, [5] terminal-leaf simulations, [6] evaluation-cache hits */
+ * [4] network batches launched, [5] terminal-leaf simulations, [6] evaluation-cache hits, [7] roots inherited through
+ * tree reuse (0 without it).  With tree reuse [1] counts the NEW simulations, so it is below plies x num_simulations. */
 int oth_engine_counters(oth_engine *e, int64_t out[8]);
+/* Tree-reuse statistics of the last run / stream / step-wise search (as of the last harvest or oth_search_results):
+ * out[0] inherited roots, out[1] sum of their V0 (visits the promoted child's children already held; mean V0 / S =
+ * out[1] / (out[0] * num_simulations)); *reroot_ms / *reroot_launches: HIP-event time of k_reroot and its launches during
+ * the last run (needs oth_engine_set_timing).  Any pointer may be NULL.  All zero on an engine without tree reuse.  HOST. */
+int oth_engine_reuse_stats(oth_engine *e, int64_t out[2], double *reroot_ms, int64_t *reroot_launches);
 /* Statistics of the optional evaluation cache since the run / stream began (no reference counterpart: mcts.py:71 and
  * parallel_self_play.py:106 build a fresh tree per search and evaluate every position again -- the redundancy the cache
  * removes): out[0] distinct positions evaluated (first evaluation since the cache was last cleared: compulsory misses),

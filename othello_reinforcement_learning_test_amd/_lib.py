@@ -83,6 +83,14 @@ def search_name(search):
     return "alphazero" if search_id(search) == OTH_SEARCH_ALPHAZERO else "reference"
 
 
+def check_tree_reuse(tree_reuse, search):
+    """tree_reuse is defined for search="alphazero" only (the reference's search starts every ply from an empty tree): the
+    combination with "reference" is a ValueError here, before any call into the library.  -> 0 / 1."""
+    if tree_reuse and search_id(search) != OTH_SEARCH_ALPHAZERO:
+        raise ValueError('tree_reuse=True needs search="alphazero", got search=%r' % (search,))
+    return 1 if tree_reuse else 0
+
+
 def common_rules(boards, expected=None):
     """The one rule set of a list of board objects (their class attribute ``rules``; objects without one play the
     reference's game).  A mix -- among the boards, or with `expected` -- is refused with a ValueError."""
@@ -169,10 +177,12 @@ _SIGS = {
     "oth_net_get_act_scale": (C.c_int, [vp, f32p]),
     "oth_policy_exp": (C.c_int, [vp, vp, C.c_int64, vp]),
     "oth_engine_create": (vp, [C.POINTER(EngineCfg)]),
+    "oth_engine_create_reuse": (vp, [C.POINTER(EngineCfg), C.c_int32]),
     "oth_engine_destroy": (None, [vp]),
     "oth_engine_set_net": (C.c_int, [vp, vp]),
     "oth_engine_set_root_noise": (C.c_int, [vp, C.c_int32, C.c_uint64]),
     "oth_search_begin": (C.c_int, [vp, u64p, u64p, C.c_int32, vp]),
+    "oth_search_advance": (C.c_int, [vp, i32p, vp]),
     "oth_search_select": (C.c_int, [vp, vp]),
     "oth_search_leaves": (C.c_int, [vp, i32p, u64p, u64p, u64p, vp]),
     "oth_search_expand": (C.c_int, [vp, vp, vp, C.c_int32, vp]),
@@ -191,6 +201,7 @@ _SIGS = {
     "oth_engine_snapshot": (C.c_int, [vp, vp]),
     "oth_engine_restore": (C.c_int, [vp, vp]),
     "oth_engine_counters": (C.c_int, [vp, i64p]),
+    "oth_engine_reuse_stats": (C.c_int, [vp, i64p, f64p, i64p]),
     "oth_engine_cache_stats": (C.c_int, [vp, i64p, vp]),
     "oth_engine_kernel_time": (C.c_int, [vp, f64p, i64p, f64p, i64p]),
     "oth_engine_set_timing": (C.c_int, [vp, C.c_int32]),

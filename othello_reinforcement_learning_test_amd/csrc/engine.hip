@@ -21,6 +21,10 @@
 // template below, is all of the above bit for bit; kSearchAlphaZero inverts the backup sign (an edge holds the value from
 // the view of the side that chose it), counts the root's simulations in its exploration term, mixes Dirichlet noise into
 // the root priors on request and writes z from the view of the side to move at each ply.
+//
+// Tree reuse (oth_engine_create_reuse, kSearchAlphaZero only) is a further compile-time parameter U of k_tree plus one kernel of its
+// own, k_reroot: the ply step records which child's subtree a slot keeps, k_reroot compacts the arena in place so that the
+// child becomes node 0, and the next search tops the root up to num_sims visits.  The default (kReuseOff) is all of the above.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -51,7 +55,8 @@ struct __attribute__((aligned(16))) Edge {  // 16 B: one 128-bit load per lane
     uint16_t child;  // node index once expanded, 0 = not expanded (the root is never a child)
 };
 
-enum : int32_t { PEND_NONE = 0, PEND_ROOT = 1, PEND_LEAF = 2 };
+// PEND_REROOT (tree reuse only): the root is an inherited subtree (k_reroot) whose stored priors still wait for their noise
+enum : int32_t { PEND_NONE = 0, PEND_ROOT = 1, PEND_LEAF = 2, PEND_REROOT = 3 };
 enum : int { TREE_NONE = 0, TREE_SELECT = 1, TREE_PLY = 2 };       // what k_tree does after the expansion
 enum : int { ST_ACTIVE = 0, ST_DONE = 1, ST_FLAGS = 2, ST_NEXT = 3 };  // words of Dev::status
 enum : int32_t { FLAG_HIST_OVERFLOW = 1 };
@@ -61,6 +66,20 @@ constexpr int kSearchReference = 0;  // the reference's search (SURVEY 8.1 L9-L1
 constexpr int kSearchAlphaZero = 1;  // chooser's-view backup, counted root, root noise, mover's-view z
 constexpr bool search_ok(int s) { return s == kSearchReference || s == kSearchAlphaZero; }
 
+// Tree reuse (oth_engine_create_reuse, kSearchAlphaZero only) is a third compile-time selector U of the tree kernel: kReuseOff, the
+// default, is every instantiation that existed before it, instruction for instruction.  With kReuseOn the ply step keeps the
+// subtree under the move it played (it only RECORDS "re-root to child c"; k_reroot compacts), and a search tops the root's
+// children up to num_sims visits instead of adding num_sims.
+constexpr int kReuseOff = 0;
+constexpr int kReuseOn = 1;
+
+// What the reuse instantiations need beyond Dev.  A trailing kernel argument of its own, like RootNoise and for the same
+// reason: no other argument moves, and an instantiation that never reads it is unchanged.
+struct Reuse {
+    int32_t* reroot;             // [n_slots] node id the slot's tree is to be re-rooted to (0: nothing to do); written by the
+                                 // ply step / k_search_advance, consumed and cleared by k_reroot
+    unsigned long long* stats;   // [blocks][2]: inherited roots, sum of their V0 (visits the promoted child already held)
+};
 // Root Dirichlet noise of a launch (kSearchAlphaZero only).  A trailing kernel argument of its own, not a part of Dev: the
 // kernels' other arguments keep their offsets, and an instantiation that never reads it is unchanged.
 struct RootNoise {
@@ -309,7 +328,10 @@ __global__ __launch_bounds__(256) void k_root_noise(const int32_t* __restrict__ 
                                                     int n_slots, RootNoise nz) {
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= n_slots || pend[g] != PEND_ROOT) return;   // (wave-uniform)
+    if (g >= n_slots) return;
+    const int32_t pd = pend[g];
+    // (wave-uniform)  PEND_REROOT: an inherited root (k_reroot left its legal set in leaf_legal): the same draw, same counter
+    if (pd != PEND_ROOT && pd != PEND_REROOT) return;
     const uint64_t legal = leaf_legal[g];
     const bool pass = legal == 0;
     const bool has = pass ? (lane == 0) : ((legal >> lane) & 1ULL);
@@ -474,6 +496,106 @@ __device__ __forceinline__ void begin_root(const Dev& d, int g, uint64_t sb, uin
     }
 }
 
+// ---- tree reuse: re-root the arena to the child the ply step chose -----------------------------------
+// The arena is append-only, so two invariants hold for every tree expand_pending has built (and, because the compaction
+// keeps the relative order of what it keeps, for every tree k_reroot leaves behind):
+//   (1) a child's node id is greater than its parent's (a node is appended after the node whose edge links it);
+//   (2) edge_base is strictly increasing in node id, and edge_base[id] = the sum of n_children over all smaller ids.
+// One wave per slot, lane = edge rank within a node (<= 60 children).  Two ascending passes over ids c .. n_nodes-1:
+//   pass 1  remap[]: by (1) every node reachable from c is marked by a smaller id before the pass gets to it, so one ascending
+//           pass marks the children of each reachable node and numbers the reachable nodes in id order (0xFFFF: dropped);
+//   pass 2  move: a reachable node and its edges are loaded into registers (one 128-bit load per lane), the edges' child
+//           ids go through remap[] and both are stored at new_id <= id and new_base <= edge_base.  By (2) the destination
+//           of a node ends no later than the source of the next one, and a node is whole in registers before it is
+//           written (the stores take the loaded values, and a wave waits for all its lanes' loads), so storing forward in
+//           place never overwrites what is still to be read.
+// A child's new id is not known when its parent is moved in a single pass (the child comes later), hence the two passes;
+// pass 2 carries no dependence from node to node except the running edge count.
+// remap[] is dynamic LDS: 4 waves x cap_nodes x 2 B (32 KB at num_simulations = 4000).
+// Leaves the slot as a search expects it: n_nodes / n_edges, no pending leaf, the root's legal set in leaf_legal (k_root_noise
+// reads it) and pend = PEND_REROOT when the launch mixes noise in (applied by the next k_tree launch), else PEND_NONE.
+__global__ __launch_bounds__(256) void k_reroot(Dev d, Reuse ru, int noise_on) {
+    extern __shared__ uint16_t lds_remap_all[];  // [4 waves][cap_nodes]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = blockIdx.x * 4 + wave;
+    if (g >= d.n_slots) return;
+    const int c = ru.reroot[g];
+    if (c <= 0) return;   // (wave-uniform) fresh root, idle slot
+    const int nn = d.n_nodes[g];
+    if (c >= nn) {        // cannot happen (the ply step read c from a live edge); never index past the tree
+        if (lane == 0) ru.reroot[g] = 0;
+        return;
+    }
+    volatile uint16_t* remap = lds_remap_all + wave * d.cap_nodes;
+    Node* nodes = d.nodes + (size_t)g * d.cap_nodes;
+    Edge* edges = d.edges + (size_t)g * d.cap_edges;
+    constexpr uint16_t kDropped = 0xFFFF, kMarked = 0xFFFE;   // (ids are <= cap_nodes - 1 <= 4001)
+    for (int i = c + lane; i < nn; i += 64) remap[i] = kDropped;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) remap[c] = kMarked;
+    // pass 1: mark and number
+    int kept = 0;
+    for (int id = c; id < nn; ++id) {
+        if (remap[id] == kDropped) continue;   // (wave-uniform: every lane reads the same LDS word)
+        const Node nd = nodes[id];
+        int child = 0;
+        if (lane < (int)nd.n_children) child = edges[nd.edge_base + lane].child;
+        if (child > id && child < nn) remap[child] = kMarked;   // distinct children: distinct words
+        if (lane == 0) remap[id] = (uint16_t)kept;
+        ++kept;
+        __builtin_amdgcn_wave_barrier();
+    }
+    // pass 2: move
+    int new_base = 0, v0 = 0;
+    uint64_t root_legal = 0, root_self = 0, root_opp = 0;
+    for (int id = c; id < nn; ++id) {
+        const int nid = remap[id];
+        if (nid == kDropped) continue;
+        Node nd = nodes[id];
+        const bool has = lane < (int)nd.n_children;
+        Edge e{0.0, 0.0f, 0, 0};
+        if (has) e = edges[nd.edge_base + lane];
+        int ch = e.child;
+        if (ch != 0 && ch < nn) ch = remap[ch];   // (a child is always inside the tree: the bound only guards the LDS index)
+        if (id == c) {
+            v0 = wave_sum_i32(has ? (int)e.n : 0);
+            root_legal = nd.legal; root_self = nd.self_b; root_opp = nd.opp_b;
+        }
+        nd.edge_base = (uint32_t)new_base;
+        if (has) edges[new_base + lane] = Edge{e.w, e.prior, e.n, (uint16_t)ch};
+        if (lane == 0) nodes[nid] = nd;
+        new_base += (int)nd.n_children;
+    }
+    if (lane == 0) {
+        d.n_nodes[g] = kept;
+        d.n_edges[g] = new_base;
+        d.path_len[g] = 0;
+        d.eval_slot[g] = -1;   // nothing of this slot is in the evaluation batch (k_cache_insert skips it)
+        d.leaf_self[g] = root_self; d.leaf_opp[g] = root_opp; d.leaf_legal[g] = root_legal;
+        d.pend[g] = noise_on ? PEND_REROOT : PEND_NONE;
+        ru.reroot[g] = 0;
+        unsigned long long* st = ru.stats + (size_t)blockIdx.x * 2;
+        atomicAdd(&st[0], 1ULL);
+        atomicAdd(&st[1], (unsigned long long)v0);
+    }
+}
+
+// PEND_REROOT: mix the noise k_root_noise drew for this (game id, ply) into the inherited root's stored priors --
+// P' = (float)((1 - eps) * P + eps * eta), the expansion's formula on the un-noised priors the node got as an interior node.
+// The root's own edges never survive the next re-root (only a child's subtree does), so noise never compounds.
+__device__ __forceinline__ void reroot_noise(const Dev& d, int g, int lane, const RootNoise& nz) {
+    Edge* edges = d.edges + (size_t)g * d.cap_edges;
+    const Node root = d.nodes[(size_t)g * d.cap_nodes];
+    const bool pass = root.legal == 0;
+    const bool has = pass ? (lane == 0) : ((root.legal >> lane) & 1ULL);
+    const int rank = __popcll(root.legal & ((1ULL << lane) - 1ULL));
+    if (has && nz.on) {
+        float* pp = &edges[root.edge_base + rank].prior;
+        *pp = (float)((1.0 - nz.eps) * (double)*pp + nz.eps * nz.eta[(size_t)g * 64 + lane]);
+    }
+    if (lane == 0) d.pend[g] = PEND_NONE;
+}
+
 template <int BS, int R>
 __global__ __launch_bounds__(256) void k_search_begin(Dev d, const uint64_t* __restrict__ sb,
                                                       const uint64_t* __restrict__ ob, int n) {
@@ -494,6 +616,48 @@ __global__ __launch_bounds__(256) void k_search_begin(Dev d, const uint64_t* __r
     }
     if (lane == 0) { d.g_active[g] = 1; d.g_self[g] = s0; d.g_opp[g] = o0; }
     begin_root(d, g, s0, o0, legal_moves_n<BS, R>(s0, o0), slot, lane);
+}
+
+// Step-wise search with tree reuse: root g plays actions[g].  The subtree under the move is recorded for k_reroot when the
+// child exists; an unvisited move gets a fresh root (queued like a k_search_begin root); a terminal successor, action -1 or
+// an action that is not legal at the root leaves the slot idle.
+template <int BS, int R>
+__global__ __launch_bounds__(256) void k_search_advance(Dev d, Reuse ru, const int32_t* __restrict__ actions, int n) {
+    constexpr int CELLS = Geo<BS>::CELLS;
+    __shared__ BlockTally bt;
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *d.n_eval_next = 0;
+    const bool in_range = g < d.n_slots;
+    bool fresh = false, cached = false;
+    int keep = 0;
+    uint64_t sb = 0, ob = 0;
+    if (in_range && g < n && d.g_active[g] && d.pend[g] == PEND_NONE) {
+        const int action = actions[g];
+        const Node root = d.nodes[(size_t)g * d.cap_nodes];
+        const bool pass = root.legal == 0;
+        const bool ok = pass ? action == CELLS : (action >= 0 && action < CELLS && ((root.legal >> action) & 1ULL));
+        if (ok) {
+            sb = root.self_b; ob = root.opp_b;
+            apply_known_n<BS, R>(sb, ob, action);
+            if (!is_terminal_n<BS, R>(sb, ob)) {
+                const int rank = pass ? 0 : __popcll(root.legal & ((1ULL << action) - 1ULL));
+                keep = d.edges[(size_t)g * d.cap_edges + root.edge_base + rank].child;
+                fresh = keep == 0;
+            }
+        }
+    }
+    if (fresh) cached = cache_fetch(d, g, sb, ob, lane);
+    int slot = block_alloc_eval(d, bt, fresh && !cached, 0, 0, 0, 0, cached ? 1 : 0);
+    if (!in_range) return;
+    if (cached) slot = kCachedSlot;
+    if (fresh) {
+        if (lane == 0) { d.g_self[g] = sb; d.g_opp[g] = ob; ru.reroot[g] = 0; }
+        begin_root(d, g, sb, ob, legal_moves_n<BS, R>(sb, ob), slot, lane);
+    } else if (lane == 0) {
+        if (keep) { d.g_self[g] = sb; d.g_opp[g] = ob; ru.reroot[g] = keep; }
+        else { d.g_active[g] = 0; d.pend[g] = PEND_NONE; ru.reroot[g] = 0; }
+    }
 }
 
 // all slots idle; slot g < n_start joins (starts game id g) at round g * stagger / n_start (stagger 0: at once)
@@ -519,9 +683,13 @@ __global__ void k_slots_init(Dev d, int n_start, int stagger) {
 // R = rule set (othello_rules.h): only the post-shift masks inside the rules calls differ between the instantiations.
 // S = search semantics (top of this file): the backup sign, the root's parent count in the descent and the root noise of the
 // expansion differ; `nz` is read by the kSearchAlphaZero instantiations only.
-template <int MODE, int BS, int R, int S = kSearchReference>
+// U = tree reuse (kReuseOn needs kSearchAlphaZero): an inherited root's noise in phase A, the top-up budget in the descent,
+// "keep the subtree" in the ply step; `ru` is read by the kReuseOn instantiations only.
+template <int MODE, int BS, int R, int S = kSearchReference, int U = kReuseOff>
 __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ policy, const float* __restrict__ value,
-                                              int is_log, const int32_t* __restrict__ forced, int refill, RootNoise nz) {
+                                              int is_log, const int32_t* __restrict__ forced, int refill, RootNoise nz,
+                                              Reuse ru) {
+    static_assert(U == kReuseOff || S == kSearchAlphaZero, "tree reuse is defined for the alphazero search only");
     constexpr int CELLS = Geo<BS>::CELLS;
     extern __shared__ uint32_t lds_path_all[];  // [4 waves][cap_path]: the path of the current descent
     __shared__ BlockTally bt;
@@ -533,8 +701,11 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
         const int pend = in_range ? d.pend[g] : PEND_NONE;
         if constexpr (S == kSearchReference) {
             if (pend != PEND_NONE) expand_pending<BS>(d, g, lane, pend, policy, value, is_log);
-        } else {
+        } else if constexpr (U == kReuseOff) {
             if (pend != PEND_NONE) expand_pending<BS, S>(d, g, lane, pend, policy, value, is_log, nz);
+        } else {
+            if (pend == PEND_REROOT) reroot_noise(d, g, lane, nz);
+            else if (pend != PEND_NONE) expand_pending<BS, S>(d, g, lane, pend, policy, value, is_log, nz);
         }
     }
     if constexpr (MODE == TREE_NONE) return;
@@ -545,6 +716,7 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
     if constexpr (MODE == TREE_SELECT) {
         volatile uint32_t* lpath = lds_path_all + (threadIdx.x >> 6) * d.cap_path;
         bool need = false, terminal = false, cached = false;
+        [[maybe_unused]] bool full = false;   // kReuseOn: the root's children already hold num_sims visits
         uint64_t sb = 0, ob = 0, lg = 0;
         int depth = 0;
         Edge* edges = nullptr;
@@ -583,6 +755,11 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                     e_n = e.n;
                     e_child = e.child;
                     if (node == 0) pv = 1 + wave_sum_i32(e_n);
+                    if constexpr (U == kReuseOn) {
+                        // top-up budget: an inherited root starts with V0 visits and runs num_sims - V0 simulations; a slot at
+                        // its budget sits the remaining select rounds out (no descent, no evaluation slot)
+                        if (node == 0 && pv - 1 >= d.num_sims) { full = true; break; }
+                    }
                     if (act) {
                         const double q = e.n == 0 ? 0.0 : e.w / (double)e.n;
                         const float cp_p = d.c_puct * e.prior;
@@ -602,12 +779,27 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                 pv = nvis;
                 node = child;
             }
+            if constexpr (U == kReuseOn) {
+                if (!full) {
+                    lg = legal_moves_n<BS, R>(sb, ob);
+                    terminal = lg == 0 && legal_moves_n<BS, R>(ob, sb) == 0;
+                    if (!terminal) cached = cache_fetch(d, g, sb, ob, lane);
+                    need = !terminal && !cached;
+                }
+            } else {
             lg = legal_moves_n<BS, R>(sb, ob);
             terminal = lg == 0 && legal_moves_n<BS, R>(ob, sb) == 0;  // bitboard.pyx:249-264
             if (!terminal) cached = cache_fetch(d, g, sb, ob, lane);
             need = !terminal && !cached;
+            }
         }
-        int slot = block_alloc_eval(d, bt, need, live ? 1 : 0, terminal ? 1 : 0, 0, 0, cached ? 1 : 0);
+        int slot;
+        if constexpr (U == kReuseOn) {
+            slot = block_alloc_eval(d, bt, need, live && !full ? 1 : 0, terminal ? 1 : 0, 0, 0, cached ? 1 : 0);
+            if (full) return;
+        } else {
+            slot = block_alloc_eval(d, bt, need, live ? 1 : 0, terminal ? 1 : 0, 0, 0, cached ? 1 : 0);
+        }
         if (!live) return;
         if (cached) slot = kCachedSlot;
         if (terminal) {  // parallel_self_play.py:133-135: back up float(get_winner()) immediately
@@ -627,6 +819,7 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
         bool next_root = false, over = false, joined = false;
         uint64_t sb = 0, ob = 0;
         int nply = 0, gid = -1;
+        [[maybe_unused]] int keep = 0;   // kReuseOn: node id of the played move's child when it has been expanded
         if (live) {
             const Node root = d.nodes[(size_t)g * d.cap_nodes];
             const Edge* edges = d.edges + (size_t)g * d.cap_edges;
@@ -712,6 +905,13 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
                 }
             } else {
                 next_root = true;
+                if constexpr (U == kReuseOn) {
+                    // the game goes on: keep the subtree under the move played when there is one (k_reroot compacts it);
+                    // an unvisited move (forced actions) gets a fresh root as without reuse
+                    const int er = pass ? 0 : __popcll(root.legal & ((1ULL << action) - 1ULL));
+                    keep = edges[root.edge_base + er].child;
+                    next_root = keep == 0;
+                }
             }
         } else if (in_range && d.g_join[g] == d.round && g < d.game_limit) {  // first game of this slot: id = slot
             gid = g;
@@ -732,6 +932,8 @@ __global__ __launch_bounds__(256) void k_tree(Dev d, const float* __restrict__ p
         if (next_root) {
             if (lane == 0) { d.g_id[g] = gid; d.g_self[g] = sb; d.g_opp[g] = ob; d.g_ply[g] = nply; }
             begin_root(d, g, sb, ob, legal_moves_n<BS, R>(sb, ob), slot, lane);
+        } else if (U == kReuseOn && keep != 0) {
+            if (lane == 0) { d.g_self[g] = sb; d.g_opp[g] = ob; d.g_ply[g] = nply; ru.reroot[g] = keep; }
         } else if (lane == 0) {
             d.g_active[g] = 0;
             d.g_id[g] = -1;
@@ -884,6 +1086,9 @@ struct oth_engine {
     int board = 8;    // board size: 8 (the reference's game) or 6
     int rules = kRulesReference;   // rule set of every rules call of this engine's kernels (cfg.rules)
     int search = kSearchReference; // search semantics of this engine's tree kernels and of its z (cfg.search)
+    bool reuse = false;            // tree_reuse of oth_engine_create_reuse: the kReuseOn instantiations of k_tree, k_reroot after every ply step
+    Reuse ru{};
+    int64_t reuse_stats[2] = {0, 0};   // inherited roots, sum of their V0 (read with the counters)
     // root noise: what oth_engine_set_root_noise asked for (step-wise search, lock-step, stream) and what the launches of
     // the current search / run carry (bound by arm_noise at its start)
     bool rn_enable = false;
@@ -906,10 +1111,10 @@ struct oth_engine {
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
-    std::vector<std::pair<size_t, int>> ev_spans;  // (index of start event, kind 0=net 1=tree)
+    std::vector<std::pair<size_t, int>> ev_spans;  // (index of start event, kind 0=net 1=tree 2=k_reroot)
     std::vector<double> net_spans;  // (start, end) ms of every network launch of the last run, on the device's reference-event axis
-    double net_ms = 0, tree_ms = 0;
-    int64_t net_launches = 0, tree_launches = 0;
+    double net_ms = 0, tree_ms = 0, reroot_ms = 0;
+    int64_t net_launches = 0, tree_launches = 0, reroot_launches = 0;
     // oth_engine_snapshot / oth_engine_restore: device copies of the small per-slot / bookkeeping arrays + the host fields
     struct Snap {
         bool valid = false;
@@ -966,6 +1171,17 @@ static inline int blocks_for(int n_slots) { return (n_slots + 3) / 4; }
     } while (0)
 #define OTH_DISPATCH_BSS(e, ...) OTH_DISPATCH_S(e, OTH_DISPATCH_BS, __VA_ARGS__)
 #define OTH_DISPATCH_BSRS(e, ...) OTH_DISPATCH_S(e, OTH_DISPATCH_BSR, __VA_ARGS__)
+// ... and k_tree's fourth constant U (tree reuse: kSearchAlphaZero engines only, checked at creation)
+#define OTH_DISPATCH_TREE(e, ...)                                     \
+    do {                                                              \
+        if ((e)->reuse) {                                             \
+            constexpr int S = kSearchAlphaZero, U = kReuseOn;         \
+            OTH_DISPATCH_BSR(e, __VA_ARGS__);                         \
+        } else {                                                      \
+            constexpr int U = kReuseOff;                              \
+            OTH_DISPATCH_BSRS(e, __VA_ARGS__);                        \
+        }                                                             \
+    } while (0)
 
 // the root noise the launches of a search / run carry: on only under kSearchAlphaZero with a positive epsilon and alpha
 static void arm_noise(oth_engine* e, bool want, uint64_t seed, bool standalone, uint32_t count) {
@@ -1038,7 +1254,8 @@ static int spans_collect(oth_engine* e) {
             OTH_HIP(hipEventElapsedTime(&t0, ref, e->ev_pool[sp.first]));
             e->net_spans.push_back((double)t0);
             e->net_spans.push_back((double)t0 + (double)ms);
-        } else { e->tree_ms += ms; e->tree_launches++; }
+        } else if (sp.second == 2) { e->reroot_ms += ms; e->reroot_launches++; }
+        else { e->tree_ms += ms; e->tree_launches++; }
     }
     e->ev_spans.clear();
     e->ev_used = 0;
@@ -1046,8 +1263,8 @@ static int spans_collect(oth_engine* e) {
 }
 static void spans_reset(oth_engine* e) {
     e->net_spans.clear();
-    e->net_ms = e->tree_ms = 0;
-    e->net_launches = e->tree_launches = 0;
+    e->net_ms = e->tree_ms = e->reroot_ms = 0;
+    e->net_launches = e->tree_launches = e->reroot_launches = 0;
     e->ev_spans.clear();
     e->ev_used = 0;
 }
@@ -1088,6 +1305,15 @@ static int launch_root_noise(oth_engine* e, hipStream_t s) {
     OTH_HIP(hipGetLastError());
     return OTH_OK;
 }
+// tree reuse: compact the subtree of every slot the launch before marked (ru.reroot); timed as a span of kind 2
+static int launch_reroot(oth_engine* e, hipStream_t s) {
+    int r = span_begin(e, s, 2);
+    if (r) return r;
+    const size_t lds = sizeof(uint16_t) * 4 * (size_t)e->d.cap_nodes;
+    hipLaunchKernelGGL(k_reroot, dim3(blocks_for(e->d.n_slots)), dim3(256), lds, s, e->d, e->ru, e->nz.on);
+    OTH_HIP(hipGetLastError());
+    return span_end(e, s);
+}
 static int launch_tree(oth_engine* e, int mode, int is_log, const int32_t* forced, int refill, hipStream_t s) {
     int r = span_begin(e, s, 1);
     if (r) return r;
@@ -1095,15 +1321,21 @@ static int launch_tree(oth_engine* e, int mode, int is_log, const int32_t* force
     const dim3 grid(blocks_for(e->d.n_slots)), block(256);
     const size_t lds = sizeof(uint32_t) * 4 * e->d.cap_path;
     if (mode == TREE_SELECT)
-        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS, R, S>), grid, block, lds, s, e->d, e->d.logp,
-                                               e->d.val, is_log, forced, refill, e->nz));
+        OTH_DISPATCH_TREE(e, hipLaunchKernelGGL((k_tree<TREE_SELECT, BS, R, S, U>), grid, block, lds, s, e->d, e->d.logp,
+                                               e->d.val, is_log, forced, refill, e->nz, e->ru));
     else if (mode == TREE_PLY)
-        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS, R, S>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
-                                               is_log, forced, refill, e->nz));
+        OTH_DISPATCH_TREE(e, hipLaunchKernelGGL((k_tree<TREE_PLY, BS, R, S, U>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
+                                               is_log, forced, refill, e->nz, e->ru));
     else
-        OTH_DISPATCH_BSRS(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS, R, S>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
-                                               is_log, forced, refill, e->nz));
+        OTH_DISPATCH_TREE(e, hipLaunchKernelGGL((k_tree<TREE_NONE, BS, R, S, U>), grid, block, 0, s, e->d, e->d.logp, e->d.val,
+                                               is_log, forced, refill, e->nz, e->ru));
     OTH_HIP(hipGetLastError());
+    if (mode == TREE_PLY && e->reuse) {   // the ply step recorded which slots keep a subtree: compact them (a span of its own)
+        if ((r = span_end(e, s))) return r;
+        if ((r = launch_reroot(e, s))) return r;
+        if (!e->nz.on) return OTH_OK;
+        if ((r = span_begin(e, s, 1))) return r;
+    }
     if (mode == TREE_PLY) {   // the ply step queued the next roots: draw their noise
         r = launch_root_noise(e, s);
         if (r) return r;
@@ -1147,6 +1379,14 @@ static int read_counters(oth_engine* e, hipStream_t s) {
         unsigned long long t = 0;
         for (size_t b = 0; b < nb; ++b) t += hc[b * 8 + i];
         e->counters[i] = (int64_t)t;
+    }
+    if (e->reuse) {
+        std::vector<unsigned long long> hs(nb * 2);
+        OTH_HIP(hipMemcpyAsync(hs.data(), e->ru.stats, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        OTH_HIP(hipStreamSynchronize(s));
+        e->reuse_stats[0] = e->reuse_stats[1] = 0;
+        for (size_t b = 0; b < nb; ++b) { e->reuse_stats[0] += (int64_t)hs[b * 2]; e->reuse_stats[1] += (int64_t)hs[b * 2 + 1]; }
+        e->counters[7] = e->reuse_stats[0];   // the one free word of oth_engine_counters; both: oth_engine_reuse_stats
     }
     return OTH_OK;
 }
@@ -1235,6 +1475,15 @@ static int harvest(oth_engine* e, int n, const int32_t* ids, int64_t* n_samples,
     return spans_collect(e);
 }
 
+// tree reuse: nothing marked for k_reroot, statistics at zero (start of a run / stream / step-wise search)
+static int reuse_reset(oth_engine* e, hipStream_t s) {
+    if (!e->reuse) return OTH_OK;
+    OTH_HIP(hipMemsetAsync(e->ru.reroot, 0, sizeof(int32_t) * (size_t)e->d.n_slots, s));
+    OTH_HIP(hipMemsetAsync(e->ru.stats, 0, sizeof(unsigned long long) * 2 * (size_t)blocks_for(e->d.n_slots), s));
+    e->reuse_stats[0] = e->reuse_stats[1] = 0;
+    return OTH_OK;
+}
+
 // common start of a batch run / lock-step run / stream: history ring, counters, status words, slots
 static int reset_run(oth_engine* e, int hist_games, int game_limit, int n_start, int stagger, uint64_t seed, hipStream_t s) {
     int r = ensure_history(e, hist_games);
@@ -1242,6 +1491,8 @@ static int reset_run(oth_engine* e, int hist_games, int game_limit, int n_start,
     OTH_HIP(hipMemsetAsync(e->d.game_len, 0xFF, sizeof(int32_t) * (size_t)e->hist_cap, s));  // -1: free
     OTH_HIP(hipMemsetAsync(e->d.counters, 0, sizeof(unsigned long long) * 8 * (size_t)blocks_for(e->d.n_slots), s));
     if (e->d.cmask) OTH_HIP(hipMemsetAsync(e->d.cstat, 0, sizeof(unsigned long long) * 4 * (size_t)blocks_for(e->d.n_slots), s));
+    int rr = reuse_reset(e, s);
+    if (rr) return rr;
     const int32_t st[4] = {0, 0, 0, n_start};
     OTH_HIP(hipMemcpyAsync(e->d.status, st, sizeof(st), hipMemcpyHostToDevice, s));
     OTH_HIP(hipStreamSynchronize(s));  // `st` lives on this stack frame
@@ -1288,9 +1539,8 @@ static int poll_wait(oth_engine* e, int round, const int32_t** st) {
     return OTH_OK;
 }
 
-extern "C" {
-
-oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
+// oth_engine_create / oth_engine_create_reuse: oth_engine_cfg keeps its layout, the reuse option travels beside it
+static oth_engine* engine_create(const oth_engine_cfg* cfg, int32_t tree_reuse) {
     if (!device_ok()) {
         set_error("oth_engine_create: no gfx950 (MI355X) device available; there is no CPU fallback");
         return nullptr;
@@ -1313,8 +1563,18 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
                   (int)cfg->search);
         return nullptr;
     }
+    if (!(tree_reuse == 0 || tree_reuse == 1)) {
+        set_error("oth_engine_create_reuse: tree_reuse must be 0 or 1, got %d", (int)tree_reuse);
+        return nullptr;
+    }
+    if (tree_reuse && cfg->search != kSearchAlphaZero) {
+        set_error("oth_engine_create_reuse: tree_reuse = 1 needs search = OTH_SEARCH_ALPHAZERO (the reference's search starts every "
+                  "ply from an empty tree: that is its contract)");
+        return nullptr;
+    }
     oth_engine* e = new oth_engine();
     e->device = current_device();
+    e->reuse = tree_reuse != 0;
     e->cfg = *cfg;
     e->board = cfg->board_size == 6 ? 6 : 8;
     e->rules = cfg->rules;
@@ -1368,6 +1628,10 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
         }
     }
     if (e->search == kSearchAlphaZero) r |= dev_alloc(e, &e->nz.eta, (size_t)G * 64);   // root noise draws, one row per slot
+    if (e->reuse) {
+        r |= dev_alloc(e, &e->ru.reroot, G);
+        r |= dev_alloc(e, &e->ru.stats, (size_t)blocks_for(G) * 2);
+    }
     double* st = nullptr;
     r |= dev_alloc(e, &st, (size_t)S + 4);
     if (!r && hipHostMalloc((void**)&e->h_status, sizeof(int32_t) * 8) != hipSuccess) r = 1;
@@ -1391,6 +1655,11 @@ oth_engine* oth_engine_create(const oth_engine_cfg* cfg) {
     d.sqrt_tab = st;
     return e;
 }
+
+extern "C" {
+
+oth_engine* oth_engine_create(const oth_engine_cfg* cfg) { return engine_create(cfg, 0); }
+oth_engine* oth_engine_create_reuse(const oth_engine_cfg* cfg, int32_t tree_reuse) { return engine_create(cfg, tree_reuse); }
 
 void oth_engine_destroy(oth_engine* e) {
     if (!e) return;
@@ -1438,6 +1707,7 @@ int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int3
     spans_reset(e);
     int rc = reset_cursors(e, s);
     if (rc) return rc;
+    if ((rc = reuse_reset(e, s))) return rc;
     if ((rc = cache_clear(e, s))) return rc;
     bind_cursor(e);
     OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_search_begin<BS, R>), dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d,
@@ -1446,6 +1716,26 @@ int oth_search_begin(oth_engine* e, const uint64_t* sb, const uint64_t* ob, int3
     if ((rc = launch_root_noise(e, s))) return rc;
     e->n_roots = n;
     return OTH_OK;
+}
+
+int oth_search_advance(oth_engine* e, const int32_t* actions, void* stream) {
+    OTH_NEED_DEVICE();
+    OTH_CHECK(e && actions, "oth_search_advance: null argument");
+    OTH_CHECK(e->reuse, "oth_search_advance: the engine was created without tree_reuse");
+    OTH_CHECK(e->n_roots > 0 && !e->lockstep && !e->streaming, "oth_search_advance: call oth_search_begin first");
+    OTH_BIND(e->device);
+    hipStream_t s = as_stream(stream);
+    arm_noise(e, e->rn_enable, e->rn_seed, true, e->rn_begins++);   // the counter advances as at a begin
+    int32_t* dact = e->r_act;
+    OTH_HIP(hipMemsetAsync(dact, 0xFF, sizeof(int32_t) * e->d.n_slots, s));
+    OTH_HIP(hipMemcpyAsync(dact, actions, sizeof(int32_t) * e->n_roots, hipMemcpyDefault, s));
+    bind_cursor(e);
+    OTH_DISPATCH_BSR(e, hipLaunchKernelGGL((k_search_advance<BS, R>), dim3(blocks_for(e->d.n_slots)), dim3(256), 0, s, e->d,
+                                          e->ru, dact, e->n_roots));
+    OTH_HIP(hipGetLastError());
+    int rc = launch_reroot(e, s);
+    if (rc) return rc;
+    return launch_root_noise(e, s);
 }
 
 int oth_search_select(oth_engine* e, void* stream) {
@@ -1704,11 +1994,13 @@ int oth_stream_step(oth_engine* e, int32_t min_games, int32_t* n_games, int64_t*
 }
 
 // ---- snapshot / restore (the rescue of a saturated fp16-split launch: see oth_net_saturated in the header) --------------
-// At a call boundary every playing slot is in the state begin_root left it in: an empty tree (n_nodes = n_edges = 0), its
-// root queued (leaf_*, eval_slot, pend = PEND_ROOT, the dense evaluation batch and its cursor) or taken from the evaluation
-// cache (cres).  So the node / edge / path arenas need no copy -- the per-slot words, the batch, the status words, the
-// counters and the ring's bookkeeping do (hist_bits / hist_pi are append-only per (game, ply): a replayed ply rewrites
-// its own entry).
+// Without tree reuse, every playing slot is at a call boundary in the state begin_root left it in: an empty tree (n_nodes =
+// n_edges = 0), its root queued (leaf_*, eval_slot, pend = PEND_ROOT, the dense evaluation batch and its cursor) or taken
+// from the evaluation cache (cres).  So the node / edge / path arenas need no copy -- the per-slot words, the batch, the status
+// words, the counters and the ring's bookkeeping do (hist_bits / hist_pi are append-only per (game, ply): a replayed ply
+// rewrites its own entry).  WITH tree reuse a slot carries its inherited subtree across the boundary, so the node and edge
+// arenas are copied too (device to device, a few hundred MB at the flagship shape, once per step); the path arena is still
+// empty at a boundary (k_reroot leaves path_len = 0).
 int oth_engine_snapshot(oth_engine* e, void* stream) {
     OTH_NEED_DEVICE();
     OTH_CHECK(e && (e->streaming || e->lockstep), "oth_engine_snapshot: no stream or lock-step run in progress");
@@ -1720,7 +2012,7 @@ int oth_engine_snapshot(oth_engine* e, void* stream) {
         sn.copies.clear();
         sn.regions.clear();
         const Dev& d = e->d;
-        const void* skip[] = {d.nodes, d.edges, d.path, d.ck, d.cv, d.clk, d.cseen, d.sqrt_tab, e->r_pi, e->r_prior, e->r_visits,
+        const void* skip[] = {e->reuse ? nullptr : (const void*)d.nodes, e->reuse ? nullptr : (const void*)d.edges, d.path, d.ck, d.cv, d.clk, d.cseen, d.sqrt_tab, e->r_pi, e->r_prior, e->r_visits,
                               e->r_wsum, e->r_act, e->d_total};
         for (size_t i = 0; i < e->allocs.size(); ++i) {
             bool sk = false;
@@ -1835,6 +2127,14 @@ int oth_engine_cache_stats(oth_engine* e, int64_t out[4], void* stream) {
     OTH_HIP(hipStreamSynchronize(s));
     for (size_t b = 0; b < nb; ++b)
         for (int i = 0; i < 3; ++i) out[i] += (int64_t)h[b * 4 + i];
+    return OTH_OK;
+}
+
+int oth_engine_reuse_stats(oth_engine* e, int64_t out[2], double* reroot_ms, int64_t* reroot_launches) {
+    OTH_CHECK(e, "oth_engine_reuse_stats: null engine");
+    if (out) { out[0] = e->reuse_stats[0]; out[1] = e->reuse_stats[1]; }
+    if (reroot_ms) *reroot_ms = e->reroot_ms;
+    if (reroot_launches) *reroot_launches = e->reroot_launches;
     return OTH_OK;
 }
 

@@ -467,12 +467,15 @@ class SearchEngine:
 
     def __init__(self, max_games, num_simulations, temperature_threshold=15, c_puct=1.0,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, store_late_onehot=False, evaluator=None,
-                 eval_cache_log2=0, board_size=None, rules="reference", search="reference"):
+                 eval_cache_log2=0, board_size=None, rules="reference", search="reference", tree_reuse=False):
         # (both names are checked before any device call: an unknown one is a ValueError with or without a GPU)
         self.rules = _lib.rules_name(rules)   # "reference" (the default: the reference's game) or "othello" (standard)
         # "reference" (the default: the reference's search, SURVEY 8.1 L9-L16 included) or "alphazero": child values from the
         # view of the side that chose the move, a root that counts its simulations, root Dirichlet noise, z from the mover's view
         self.search = _lib.search_name(search)
+        # opt-in tree reuse (search="alphazero" only: a ValueError otherwise, before any call into the library): the subtree
+        # under the move played becomes the next ply's tree and a search tops the root up to num_simulations visits
+        self.tree_reuse = bool(_lib.check_tree_reuse(tree_reuse, search))
         _lib.require_device()
         self._noise = (False, 0)
         self.max_games = int(max_games)
@@ -486,7 +489,10 @@ class SearchEngine:
                              float(c_puct), float(dirichlet_alpha), float(dirichlet_epsilon),
                              1 if store_late_onehot else 0, int(eval_cache_log2), self.board_size,
                              _lib.rules_id(rules), _lib.search_id(search))
-        self._h = _lib.load().oth_engine_create(C.byref(cfg))
+        if self.tree_reuse:   # (the option is an argument of its own creation call: oth_engine_cfg keeps its layout)
+            self._h = _lib.load().oth_engine_create_reuse(C.byref(cfg), 1)
+        else:
+            self._h = _lib.load().oth_engine_create(C.byref(cfg))
         if not self._h:
             raise _lib.OthelloHipError("oth_engine_create: " + _lib.last_error())
         self.evaluator = None
@@ -514,6 +520,34 @@ class SearchEngine:
         self._roots = (s.copy(), o.copy())
         _lib.call("oth_search_begin", self._h, _lib.np_ptr(s, C.c_uint64), _lib.np_ptr(o, C.c_uint64),
                   self._n, _lib.current_stream())
+
+    def search_advance(self, actions):
+        """Tree reuse in the step-wise search (an engine built with tree_reuse=True): root i plays actions[i] (-1: the
+        root goes idle).  Where the move's child was expanded its subtree becomes the tree; otherwise a fresh root is
+        queued and comes out of search_leaves / goes into search_expand like a search_begin root; a terminal successor
+        leaves the root idle.  search_select / search_run then top every root up to num_simulations visits."""
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        if len(a) != self._n:
+            raise ValueError("search_advance: %d actions for %d roots" % (len(a), self._n))
+        lib = _lib.load()
+        s, o = self._roots
+        for i, act in enumerate(a):   # the host's copy of the root positions (search_results at a general temperature)
+            if act >= 0:
+                b = _lib.Board(int(s[i]), int(o[i]), 0, 0)
+                lib.oth_board_make_move_r(self.board_size, _lib.rules_id(self.rules), C.byref(b), int(act))
+                s[i], o[i] = b.self_board, b.opp_board
+        _lib.call("oth_search_advance", self._h, _lib.np_ptr(a, C.c_int32), _lib.current_stream())
+
+    def reuse_stats(self):
+        """Tree-reuse statistics of the last run / stream / step-wise search: roots that inherited a subtree, the visits
+        they inherited (sum of V0), mean V0 / num_simulations, and k_reroot's HIP-event time (set_timing(True))."""
+        out = (C.c_int64 * 2)()
+        ms, nl = C.c_double(0), C.c_int64(0)
+        _lib.call("oth_engine_reuse_stats", self._h, out, C.byref(ms), C.byref(nl))
+        roots, v0 = int(out[0]), int(out[1])
+        frac = v0 / (roots * self.num_simulations) if roots and self.num_simulations else 0.0
+        return {"inherited_roots": roots, "inherited_visits": v0, "mean_v0_over_s": frac,
+                "reroot_ms": ms.value, "reroot_launches": nl.value}
 
     def search_select(self):
         _lib.call("oth_search_select", self._h, _lib.current_stream())

@@ -28,8 +28,11 @@ class BatchMCTS:
     (parallel_self_play.py:80-170)."""
 
     def __init__(self, model, device=None, c_puct=1.0, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
-                 precision=None, evaluator=None, search="reference"):
+                 precision=None, evaluator=None, search="reference", tree_reuse=False):
         self.search = _lib.search_name(search)
+        # tree reuse (search="alphazero" only): the engines of this object are built with it, so a caller that drives one
+        # step-wise (SearchEngine.search_advance) keeps its trees; search_batch itself stays stateless per call
+        self.tree_reuse = bool(_lib.check_tree_reuse(tree_reuse, self.search))
         self.model = model
         self.device = device
         self.c_puct = c_puct
@@ -53,7 +56,7 @@ class BatchMCTS:
                                dirichlet_alpha=self.dirichlet_alpha,
                                dirichlet_epsilon=self.dirichlet_epsilon,
                                evaluator=None if self._external else self.evaluator, rules=rules,
-                               search=self.search)
+                               search=self.search, tree_reuse=self.tree_reuse)
             self._engines[key] = eng
         return eng
 
@@ -89,8 +92,11 @@ class ParallelSelfPlayWorker:
     def __init__(self, board_class, model, device=None, num_simulations=25, temperature_threshold=15,
                  num_parallel_games=8, c_puct=1.0, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
                  rng_mode=None, precision=None, verbose=True, eval_cache_log2=0, lanes=None, continuous=False,
-                 stagger_rounds=0, device_slots=None, search="reference"):
+                 stagger_rounds=0, device_slots=None, search="reference", tree_reuse=False):
         self.board_class = board_class
+        # tree reuse (opt-in, search="alphazero" only; YAML key mcts.tree_reuse): every engine of this worker -- its own, the
+        # lane engines, a grown engine, the stream -- keeps the subtree under the move played and tops it up to num_simulations
+        self.tree_reuse = bool(_lib.check_tree_reuse(tree_reuse, search))
         # the search semantics of every engine of this worker (its own, the lane engines, a grown engine)
         self.search = _lib.search_name(search)
         # the rule set every engine of this worker plays (lane engines and a grown engine included) and the class of the
@@ -104,7 +110,7 @@ class ParallelSelfPlayWorker:
             raise ValueError("rng_mode must be 'device' or 'numpy'")
         self.verbose = verbose
         self.batch_mcts = BatchMCTS(model, device, c_puct, dirichlet_alpha, dirichlet_epsilon,
-                                    precision=precision, search=self.search)
+                                    precision=precision, search=self.search, tree_reuse=self.tree_reuse)
         # device_slots: game slots of the engine in device-RNG mode.  The reference's num_parallel_games (8-32 in its
         # configs, parallel_self_play.py:232) is how many games share one network batch; with the counter-based RNG a
         # game's tuples depend on (seed, game id) only, so playing MORE games of a call at once changes nothing but the
@@ -115,12 +121,13 @@ class ParallelSelfPlayWorker:
         self._engine_args = dict(temperature_threshold=temperature_threshold, c_puct=c_puct,
                                  dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                                  store_late_onehot=False, eval_cache_log2=eval_cache_log2, rules=self.rules,
-                                 search=self.search)
+                                 search=self.search, tree_reuse=self.tree_reuse)
         self.engine = SearchEngine(self.device_slots or num_parallel_games, num_simulations,
                                    temperature_threshold=temperature_threshold, c_puct=c_puct,
                                    dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                                    store_late_onehot=False, evaluator=self.batch_mcts.evaluator,
-                                   eval_cache_log2=eval_cache_log2, rules=self.rules, search=self.search)
+                                   eval_cache_log2=eval_cache_log2, rules=self.rules, search=self.search,
+                                   tree_reuse=self.tree_reuse)
         # lanes > 1 (device RNG mode): the slots are split into independent groups, each an engine on its own
         # stream and host thread; their kernels overlap on the device (one group's network launches fill the
         # other's tails and tree-search phases: +4 % at 4096 slots).  Results are concatenated lane by lane.
@@ -134,7 +141,7 @@ class ParallelSelfPlayWorker:
                                                c_puct=c_puct, dirichlet_alpha=dirichlet_alpha,
                                                dirichlet_epsilon=dirichlet_epsilon, store_late_onehot=False,
                                                evaluator=self.batch_mcts.evaluator, eval_cache_log2=eval_cache_log2,
-                                               rules=self.rules, search=self.search)
+                                               rules=self.rules, search=self.search, tree_reuse=self.tree_reuse)
                                   for _ in range(self.lanes)]
         # continuous=True (device RNG only): the slots keep playing BETWEEN execute_episodes calls (oth_stream_*): a call
         # returns the games that finished during it -- at least num_episodes -- and leaves the others in flight, so
@@ -308,10 +315,14 @@ class ParallelSelfPlayWorker:
         for eng in (self._ran if self.rng_mode == "device" else [self.engine]):
             for k, v in eng.counters().items():
                 counters[k] = counters.get(k, 0) + v
+            if self.tree_reuse:   # roots that inherited a subtree and the visits they inherited (mean V0 / S: reuse_stats)
+                rs = eng.reuse_stats()
+                for k in ("inherited_roots", "inherited_visits"):
+                    counters[k] = counters.get(k, 0) + rs[k]
         games = len(self.last_game_ids) if (self.continuous and self.rng_mode == "device") else num_episodes
         ev = self.batch_mcts.evaluator
         # what the run's arithmetic was: the activation scale of the fp16-split trunk and every rescue so far
-        counters.update({"rules": self.rules, "search": self.search, "precision": getattr(ev, "precision", None), "act_scale": getattr(ev, "act_scale", None),
+        counters.update({"rules": self.rules, "search": self.search, "tree_reuse": self.tree_reuse, "precision": getattr(ev, "precision", None), "act_scale": getattr(ev, "act_scale", None),
                          "rescues": len(getattr(ev, "rescues", ()))})
         if self._lane_check is not None and self._ran is self._lane_engines:
             counters.update(self._lane_check.report())
@@ -349,6 +360,10 @@ def create_parallel_self_play_worker(config, model, device=None, **kwargs):
     # `mcts.semantics` -- a key of THIS package (absent = "reference" = the reference's search): "alphazero" selects the
     # opt-in search semantics.  A keyword argument `search` wins.
     kwargs.setdefault("search", _lib.search_name(mcts.get("semantics", "reference")))
+    # `mcts.tree_reuse` -- a key of THIS package (absent = off): keep the subtree under the move played between plies; needs
+    # mcts.semantics: alphazero.  A keyword argument `tree_reuse` wins.
+    if "tree_reuse" in mcts:
+        kwargs.setdefault("tree_reuse", bool(mcts["tree_reuse"]))
     # `self_play.continuous: true` -- a key of THIS package, absent from the reference's YAML files (absent = off = the
     # reference's call-by-call behaviour): the worker's slots keep playing between execute_episodes calls, so a trainer that
     # asks for 50-200 episodes per iteration (training.self_play_episodes_per_iter: 100 in configs/default_8x8.yaml, 50 in fast_8x8) is

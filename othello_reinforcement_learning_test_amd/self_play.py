@@ -51,12 +51,16 @@ def tuples_from_arrays(states, pis, zs, block=512):
 
 
 class SelfPlayWorker:
-    def __init__(self, board_class, mcts, num_simulations=25, temperature_threshold=15, rng_mode=None, search=None):
+    def __init__(self, board_class, mcts, num_simulations=25, temperature_threshold=15, rng_mode=None, search=None,
+                 tree_reuse=False):
         self.board_class = board_class
         own = getattr(mcts, "search_semantics", "reference")
         self.search = _lib.search_name(own if search is None else search)
         if self.search != own:   # the numpy mode searches through `mcts`, the device mode through an engine of this worker
             raise ValueError("search=%r, but the MCTS object was built with search=%r" % (self.search, own))
+        # tree reuse (search="alphazero" only) applies to the device path: its engine keeps the subtree under the move played.
+        # The numpy mode searches through MCTS.search, which stays stateless per call.
+        self.tree_reuse = bool(_lib.check_tree_reuse(tree_reuse, self.search))
         self.rules = _lib.rules_name(getattr(board_class, "rules", "reference"))   # the device engine plays the class's rules
         self.mcts = mcts
         self.num_simulations = num_simulations
@@ -99,7 +103,7 @@ class SelfPlayWorker:
                 g, self.num_simulations, temperature_threshold=self.temperature_threshold,
                 c_puct=self.mcts.c_puct, dirichlet_alpha=self.mcts.dirichlet_alpha,
                 dirichlet_epsilon=self.mcts.dirichlet_epsilon, store_late_onehot=True,
-                evaluator=self.mcts.evaluator, rules=self.rules, search=self.search)
+                evaluator=self.mcts.evaluator, rules=self.rules, search=self.search, tree_reuse=self.tree_reuse)
         return self._engine
 
     def execute_episodes(self, num_episodes, add_dirichlet_noise=True):

@@ -1,0 +1,465 @@
+"""Opt-in tree reuse on the device (search="alphazero", tree_reuse=True) against its Python definition
+(tests/reuse_search_ref.py), bit for bit: the compaction alone, the continued search over whole scripted games, lock-step
+self-play with the HIP network, batch run = lock-step, streams, root noise at a re-root, snapshot / restore, refusals."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import az_search_ref as az
+import reuse_search_ref as rr
+import std_rules_ref as sr
+from test_gpu_az_search import bits_of, check_stream_az, hip_eval_fn
+
+pytestmark = pytest.mark.gpu
+U64 = np.uint64
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import othello_reinforcement_learning_test_amd as p
+    p._lib.require_device()
+    return p
+
+
+def feed(eng, batch):
+    """Evaluate the queued positions with `batch` and expand them.  -> how many there were."""
+    s, o, lg = eng.search_leaves()
+    if len(s):
+        p, v = batch(s, o, lg)
+    else:
+        p, v = np.zeros((1, eng.npol), F32), np.zeros(1, F32)
+    eng.search_expand(p, v, is_log=False)
+    return len(s)
+
+
+def drive(pkg, case, check_post):
+    """Play the scripted games of `case` on an 8-slot engine through the step-wise search with the case's evaluator.
+    Always: right after search_begin / search_advance (+ the expansion of the fresh roots), BEFORE any new simulation, the
+    root statistics equal the Python tree's (an inherited root: the promoted child's visits, float64 W and float32 priors).
+    check_post: every ply's visits, W, priors and pi after the top-up equal the definition too."""
+    family, bs, name, sims, roots = case
+    rows = rr.scripted_games(case)
+    _, batch = rr.evaluator(family, bs)
+    eng = pkg.SearchEngine(8, sims, c_puct=1.0, board_size=bs, rules=name, search="alphazero", tree_reuse=True)
+    assert eng.tree_reuse and eng.search == "alphazero"
+    s0, o0 = sr.start_position(bs)
+    eng.search_begin([s0] * roots, [o0] * roots)
+    assert feed(eng, batch) == roots
+    total_new = inherited = v0_sum = 0
+    for p, row in enumerate(rows):
+        live = [g for g, rec in enumerate(row) if rec is not None]
+        _, visits, wsum, prior = eng.search_results()
+        for g in live:
+            wv, ww, wp, _ = row[g]["pre"]
+            assert np.array_equal(visits[g], wv), "ply %d game %d: visits after the re-root" % (p, g)
+            assert np.array_equal(wsum[g], ww), "ply %d game %d: W after the re-root" % (p, g)
+            assert np.array_equal(prior[g], wp), "ply %d game %d: priors after the re-root" % (p, g)
+        need = max(row[g]["new"] for g in live)
+        for r in range(sims if sims <= 64 else need):
+            eng.search_select()
+            n = feed(eng, batch)
+            if r >= need:
+                assert n == 0, "a slot at its budget sits the round out"
+        eng.search_select()                    # one round past every budget: no descent, no evaluation slot
+        assert feed(eng, batch) == 0
+        if check_post:
+            pi, visits, wsum, prior = eng.search_results()
+            for g in live:
+                wv, ww, wp, wpi = row[g]["post"]
+                assert np.array_equal(visits[g], wv), "ply %d game %d: visits" % (p, g)
+                assert np.array_equal(wsum[g], ww), "ply %d game %d: W" % (p, g)
+                assert np.array_equal(prior[g], wp), "ply %d game %d: priors" % (p, g)
+                assert np.array_equal(pi[g], wpi), "ply %d game %d: pi" % (p, g)
+        total_new += sum(row[g]["new"] for g in live)
+        inherited += sum(row[g]["kind"] == "inherited" for g in live)
+        v0_sum += sum(row[g]["v0"] for g in live)
+        actions = np.array([rec["action"] if rec is not None else -1 for rec in row] + [-1] * (8 - roots), dtype=np.int32)
+        eng.search_advance(actions[:roots])
+        assert feed(eng, batch) == sum(row[g]["next"] == "fresh" for g in live), "ply %d: fresh roots queued" % p
+    eng.search_results()
+    assert eng.counters()["simulations"] == total_new
+    st = eng.reuse_stats()
+    assert st["inherited_roots"] == inherited and st["inherited_visits"] == v0_sum
+    return eng
+
+
+# ---- 1. the compaction alone ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", [c for c in rr.CASES if c[3] == 6 and c[0] in ("stub", "ties")], ids=str)
+def test_reroot_keeps_the_childs_statistics(pkg, case):
+    drive(pkg, case, check_post=False)
+
+
+# ---- 2. continuation -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", rr.CASES, ids=str)
+def test_continued_search_equals_the_definition(pkg, case):
+    drive(pkg, case, check_post=True)
+
+
+# ---- 3. lock-step self-play with the HIP network -------------------------------------------------------------------------
+def lockstep_games(pkg, ev, sims, games, tree_reuse, script=None):
+    """Whole lock-step games.  script=None: the actions are chosen here (on every third ply a seeded UNVISITED legal move when
+    there is one, else any seeded legal move; on the other plies a seeded move of positive pi) and pi is compared with ReuseSearch per ply; else they are replayed.
+    -> dict(tuples, gl, actions per ply, new simulations of the definition, counters)."""
+    eng = pkg.SearchEngine(games, sims, temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero",
+                           tree_reuse=tree_reuse)
+    rules = rr.rules_obj(8, "othello")
+    fn = hip_eval_fn(ev, games, 8)
+    searches = [rr.ReuseSearch(rules, sims, 1.0, fn) for _ in range(games)]
+    for rs in searches:
+        rs.begin(*sr.start_position(8))
+    over, plies = [False] * games, [0] * games
+    rng = np.random.Generator(np.random.PCG64(2))
+    played, new_total, unvisited = [], 0, 0
+    eng.selfplay_begin(games)
+    for ply in range(128):
+        if all(over):
+            break
+        pi, active = eng.selfplay_search()
+        assert active.tolist() == [0 if f else 1 for f in over]
+        actions = np.zeros(games, dtype=np.int32)
+        for i, rs in enumerate(searches):
+            if over[i]:
+                continue
+            if script is None:
+                new_total += rs.top_up()[1]
+                assert np.array_equal(pi[i], rs.results()[3]), "game %d ply %d" % (i, ply)
+                legal = sr.legal_actions(rules, *rs.pos)
+                cold = [m for m in legal if pi[i][m] == 0]
+                moves = (cold or legal) if ply % 3 == 2 else np.flatnonzero(pi[i] > 0)
+                a = int(moves[int(rng.integers(len(moves)))])
+                unvisited += pi[i][a] == 0
+            else:
+                a = int(script[ply][i])
+            actions[i], plies[i] = a, plies[i] + 1
+            if script is None:
+                over[i] = rs.advance(a) == "over"
+            else:
+                rs.pos = sr.apply_move(rules, *rs.pos, a)
+                over[i] = rules.legal(*rs.pos) == 0 and rules.legal(rs.pos[1], rs.pos[0]) == 0
+        played.append(actions.copy())
+        assert eng.selfplay_apply(actions) == over.count(False)
+    assert all(over)
+    n = eng.selfplay_end()
+    st, p, z, gl = eng.selfplay_fetch(n)
+    assert gl.tolist() == plies and n == sum(plies)
+    return dict(tuples=(st, p, z), gl=gl, actions=played, new=new_total, unvisited=unvisited, counters=eng.counters(),
+                reuse=eng.reuse_stats())
+
+
+@pytest.mark.parametrize("sims", [6, 24])
+def test_lockstep_selfplay_with_reuse_equals_the_definition(pkg, sims):
+    """pi per ply is the definition's, bit for bit, over whole games whose forced actions include unvisited moves; z and
+    the stream's shape go through check_stream_az (which links consecutive positions by a move of positive pi: the forced
+    unvisited moves are marked in a COPY of pi with 1e-9, below its 1e-6 bound on the sum); counter [1] is the definition's
+    number of new simulations; evaluations fall below the same games without reuse."""
+    torch.manual_seed(8)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    games = 4
+    got = lockstep_games(pkg, ev, sims, games, True)
+    # every third ply plays an unvisited legal move WHEN THERE IS ONE.  At S = 6 there always is (more legal moves than
+    # simulations); at S = 24 a seeded 2x16 network's near-equal priors and near-zero values make PUCT visit every one of
+    # the (at most ~20) legal moves once before it returns to any, so no position of these games has one: the script then
+    # plays a seeded legal move, and the count is printed
+    print("S = %d: forced unvisited moves: %d" % (sims, got["unvisited"]))
+    if sims == 6:
+        assert got["unvisited"] >= 1, "no forced unvisited move in the scripted lock-step games"
+    st, p, z = got["tuples"]
+    marked = p.copy()
+    t = 0
+    for g in range(games):
+        for ply in range(int(got["gl"][g])):
+            a = int(got["actions"][ply][g])
+            if marked[t, a] == 0:
+                marked[t, a] = 1e-9
+            t += 1
+    check_stream_az(8, "othello", st, marked, z, games, got["gl"])
+    assert got["counters"]["simulations"] == got["new"] < got["counters"]["plies"] * sims
+    assert got["reuse"]["inherited_roots"] >= 1
+    plain = lockstep_games(pkg, ev, sims, games, False, script=got["actions"])
+    assert plain["counters"]["simulations"] == plain["counters"]["plies"] * sims
+    assert np.array_equal(plain["tuples"][0], st) and np.array_equal(plain["tuples"][2], z)     # the same games
+    assert got["counters"]["evals"] < plain["counters"]["evals"]
+    print("S = %d: evaluations %d with reuse, %d without; new simulations %d of %d" %
+          (sims, got["counters"]["evals"], plain["counters"]["evals"], got["new"], got["counters"]["plies"] * sims))
+
+
+# ---- 4. batch run = lock-step ---------------------------------------------------------------------------------------------
+def actions_of(states, zs, gl, rules, bs=8):
+    """The actions of every game of a stream, recovered from consecutive states (the last one: a move that ends the game
+    with the recorded z)."""
+    cells = bs * bs
+    st = states.reshape(len(states), 3, cells)
+    sb, ob = bits_of(st[:, 0]), bits_of(st[:, 1])
+    out, t = [], 0
+    for n in gl:
+        acts = []
+        for ply in range(int(n)):
+            s, o = int(sb[t]), int(ob[t])
+            found = None
+            for a in sr.legal_actions(rules, s, o):
+                cs, co = sr.apply_move(rules, s, o, a)
+                if ply + 1 < n:
+                    if (cs, co) == (int(sb[t + 1]), int(ob[t + 1])):
+                        found = a
+                        break
+                elif rules.legal(cs, co) == 0 and rules.legal(co, cs) == 0 and float(-az.winner_of(cs, co)) == float(zs[t]):
+                    found = a        # (z of the last ply is from its mover's view; the winner from the other side's)
+                    break
+            assert found is not None
+            acts.append(found)
+            t += 1
+        out.append(acts)
+    return out
+
+
+def test_batch_run_equals_lockstep_with_reuse(pkg):
+    torch.manual_seed(3)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    kw = dict(temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero", tree_reuse=True)
+    eng = pkg.SearchEngine(8, 6, **kw)
+    n = eng.selfplay_run(8, 41, add_noise=True)
+    st, p, z, gl = eng.selfplay_fetch(n)
+    assert eng.reuse_stats()["inherited_roots"] >= 1 and eng.counters()["simulations"] < eng.counters()["plies"] * 6
+    acts = actions_of(st, z, gl, rr.rules_obj(8, "othello"))
+    two = pkg.SearchEngine(8, 6, **kw)
+    two.set_root_noise(True, 41)              # a lock-step run keys its noise by (game id, ply) under this seed
+    two.selfplay_begin(8)
+    for ply in range(int(gl.max())):
+        two.selfplay_search()
+        two.selfplay_apply(np.array([a[ply] if ply < len(a) else 0 for a in acts], dtype=np.int32))
+    m = two.selfplay_end()
+    st2, p2, z2, gl2 = two.selfplay_fetch(m)
+    assert m == n and np.array_equal(gl, gl2)
+    assert np.array_equal(st, st2) and np.array_equal(p, p2) and np.array_equal(z, z2)
+    assert two.counters()["simulations"] == eng.counters()["simulations"]
+
+
+# ---- 5. streams -----------------------------------------------------------------------------------------------------------
+def by_id(ids, st, p, z, gl):
+    out, t = {}, 0
+    for g, n in zip(ids, gl):
+        out[int(g)] = (st[t:t + n], p[t:t + n], z[t:t + n])
+        t += int(n)
+    return out
+
+
+def assert_same_games(a, b, least):
+    common = sorted(set(a) & set(b))
+    assert len(common) >= least
+    for g in common:
+        for x, y in zip(a[g], b[g]):
+            assert np.array_equal(x, y), "game %d" % g
+
+
+def test_stream_with_reuse_depends_on_the_seed_and_the_game_id_only(pkg):
+    torch.manual_seed(3)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    games = {}
+    for step in (3, 5):
+        eng = pkg.SearchEngine(8, 6, temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero",
+                               tree_reuse=True)
+        eng.stream_begin(17)
+        got = {}
+        while len(got) < 12:
+            g, n = eng.stream_step(step)
+            ids = eng.game_ids()
+            st, p, z, gl = eng.selfplay_fetch(n)
+            got.update(by_id(ids, st, p, z, gl))
+        games[step] = got
+        assert eng.reuse_stats()["inherited_roots"] >= 1
+    assert_same_games(games[3], games[5], 10)
+    per_lane = {}
+    for lanes in (1, 2):
+        np.random.seed(23)                    # the worker draws the stream's seed from numpy's global RNG
+        w = pkg.ParallelSelfPlayWorker(pkg.StandardOthelloBitboard, net, num_simulations=6, temperature_threshold=8,
+                                       num_parallel_games=8, verbose=False, lanes=lanes, continuous=True,
+                                       search="alphazero", tree_reuse=True)
+        assert w.tree_reuse and w.engine.tree_reuse and all(e.tree_reuse for e in w._lane_engines)
+        data = w.execute_episodes(8, add_dirichlet_noise=False)
+        ids = w.last_game_ids
+        got, t = {}, 0
+        first = [i for i, d in enumerate(data) if (d[0][:2].sum(), d[0][0].sum()) == (4.0, 2.0)]    # start positions
+        assert len(first) == len(ids)
+        for g, lo, hi in zip(ids, first, first[1:] + [len(data)]):
+            got[int(g)] = (np.stack([d[0] for d in data[lo:hi]]), np.stack([d[1] for d in data[lo:hi]]),
+                           np.array([d[2] for d in data[lo:hi]], dtype=F32))
+        per_lane[lanes] = got
+        assert w.last_stats["tree_reuse"] is True and w.last_stats["inherited_roots"] >= 1
+        assert w.last_stats["simulations"] < w.last_stats["plies"] * 6
+    assert_same_games(per_lane[1], per_lane[2], 6)
+
+
+# ---- 6. noise -------------------------------------------------------------------------------------------------------------
+ALPHA, EPS, NOISE_SEED = 0.3, 0.25, 7
+
+
+def test_noise_at_a_reroot(pkg):
+    """After a re-root the root priors are (float)((1 - eps) P + eps eta) of the inherited UN-NOISED priors P (the priors a
+    noise-free engine gives that position), eta keyed (root index, count) with the count advanced by search_advance; the
+    promoted child's own children kept un-noised priors (else the second re-root would mix noise into noisy priors); and
+    the search from the device's noisy priors is the definition's."""
+    case = ("stub", 8, "othello", 16, 5)
+    _, bs, name, sims, roots = case
+    rules = rr.rules_obj(bs, name)
+    one, batch = rr.evaluator("stub", bs)
+    eng = pkg.SearchEngine(8, sims, board_size=bs, rules=name, search="alphazero", tree_reuse=True, dirichlet_alpha=ALPHA,
+                           dirichlet_epsilon=EPS)
+    plain = pkg.SearchEngine(8, sims, board_size=bs, rules=name, search="alphazero")
+    eng.set_root_noise(True, NOISE_SEED)
+    searches = [rr.ReuseSearch(rules, sims, 1.0, one) for _ in range(roots)]
+    s0, o0 = sr.start_position(bs)
+    # five different openings: root g starts after g seeded plies
+    pos = []
+    rng = np.random.Generator(np.random.PCG64(4))
+    for g in range(roots):
+        s, o = s0, o0
+        for _ in range(g):
+            legal = sr.legal_actions(rules, s, o)
+            s, o = sr.apply_move(rules, s, o, int(legal[int(rng.integers(len(legal)))]))
+        pos.append((s, o))
+    eng.search_begin([q[0] for q in pos], [q[1] for q in pos])
+    feed(eng, batch)
+    for g, rs in enumerate(searches):
+        rs.begin(*pos[g])
+    worst, rerooted = 0.0, 0
+    for count in range(5):
+        _, _, _, prior = eng.search_results()
+        plain.search_begin([rs.pos[0] for rs in searches], [rs.pos[1] for rs in searches])
+        feed(plain, batch)
+        clean = plain.search_results()[3]
+        for g, rs in enumerate(searches):
+            legal = sr.legal_actions(rules, *rs.pos)
+            eta = az.dirichlet_ref(NOISE_SEED, g, count, len(legal), ALPHA)
+            want = ((1.0 - EPS) * clean[g, legal].astype(np.float64) + EPS * eta).astype(F32)
+            err = np.abs(prior[g, legal].astype(np.float64) - want.astype(np.float64)) / np.spacing(want).astype(np.float64)
+            worst = max(worst, float(err.max()))
+            assert (err <= 1.0).all(), "count %d root %d (%s): %s ulp from the restatement" % (
+                count, g, "inherited" if rs.inherited else "fresh", err.max())
+            assert len(legal) == 1 or not np.array_equal(prior[g, legal], clean[g, legal])
+            rerooted += bool(rs.inherited)
+            rs.set_root_prior(prior[g])
+        for _ in range(sims):
+            eng.search_select()
+            feed(eng, batch)
+        pi, visits, wsum, _ = eng.search_results()
+        actions = []
+        for g, rs in enumerate(searches):
+            rs.top_up()
+            wv, ww, _, wpi = rs.results()
+            assert np.array_equal(visits[g], wv) and np.array_equal(wsum[g], ww) and np.array_equal(pi[g], wpi), (count, g)
+            actions.append(int(np.argmax(wv)))
+            assert rs.advance(actions[-1]) == "inherited"
+        eng.search_advance(actions)
+        assert feed(eng, batch) == 0
+    assert rerooted >= 4 * roots
+    print("largest distance from the restatement: %.3g float32 ulp" % worst)
+
+
+def test_noisy_selfplay_with_reuse_is_reproducible(pkg):
+    torch.manual_seed(3)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    kw = dict(temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero", tree_reuse=True)
+
+    def run(add_noise, **more):
+        eng = pkg.SearchEngine(8, 6, **kw, **more)
+        n = eng.selfplay_run(8, 41, add_noise=add_noise)
+        return eng.selfplay_fetch(n)
+    noisy, again, plain = run(True), run(True), run(False)
+    for a, b in zip(noisy, again):
+        assert np.array_equal(a, b)
+    assert not (noisy[1].shape == plain[1].shape and np.array_equal(noisy[1], plain[1]))
+    check_stream_az(8, "othello", *noisy[:3], 8, noisy[3])
+    cached = run(True, eval_cache_log2=4)            # the cache is upstream of the tree: the same tuples
+    for a, b in zip(cached, noisy):
+        assert np.array_equal(a, b)
+
+
+# ---- 7. snapshot / restore ------------------------------------------------------------------------------------------------
+def test_snapshot_and_restore_carry_the_inherited_trees(pkg):
+    torch.manual_seed(8)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    kw = dict(temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero", tree_reuse=True)
+
+    def ply(eng, log):
+        pi, active = eng.selfplay_search()
+        log.append(pi.copy())
+        eng.selfplay_apply(np.argmax(pi, axis=1).astype(np.int32))
+
+    def finish(eng, log):
+        for _ in range(128):
+            pi, active = eng.selfplay_search()
+            if not active.any():
+                break
+            log.append(pi.copy())
+            eng.selfplay_apply(np.argmax(pi, axis=1).astype(np.int32))
+        return eng.selfplay_fetch(eng.selfplay_end())
+
+    straight, slog = pkg.SearchEngine(4, 12, **kw), []
+    straight.selfplay_begin(4)
+    want = finish(straight, slog)
+    eng, log = pkg.SearchEngine(4, 12, **kw), []
+    eng.selfplay_begin(4)
+    for _ in range(3):
+        ply(eng, log)
+    eng.snapshot()
+    first = []
+    for _ in range(2):
+        ply(eng, first)
+    eng.restore()
+    second = []
+    for _ in range(2):
+        ply(eng, second)
+    for a, b in zip(first, second):
+        assert np.array_equal(a, b), "pi of a replayed ply"
+    got = finish(eng, log)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    for a, b in zip(log[:3] + second + log[3:], slog):
+        assert np.array_equal(a, b)
+    assert eng.reuse_stats()["inherited_roots"] == straight.reuse_stats()["inherited_roots"] >= 1
+    assert eng.counters() == straight.counters()
+
+
+# ---- 8. refusals ------------------------------------------------------------------------------------------------------------
+def test_refusals_and_the_default(pkg):
+    lib = pkg._lib.load()
+    cfg = pkg._lib.EngineCfg(4, 4, 15, 1.0, 0.3, 0.25, 0, 0, 8, 0, 0)          # tree_reuse under OTH_SEARCH_REFERENCE
+    assert not lib.oth_engine_create_reuse(C.byref(cfg), 1)
+    assert "tree_reuse" in pkg._lib.last_error() and "ALPHAZERO" in pkg._lib.last_error()
+    cfg = pkg._lib.EngineCfg(4, 4, 15, 1.0, 0.3, 0.25, 0, 0, 8, 0, 1)
+    assert not lib.oth_engine_create_reuse(C.byref(cfg), 2) and "tree_reuse" in pkg._lib.last_error()
+    for reuse in (0, 1):
+        h = lib.oth_engine_create_reuse(C.byref(cfg), reuse)
+        assert h
+        lib.oth_engine_destroy(h)
+    with pytest.raises(ValueError):
+        pkg.SearchEngine(4, 4, search="reference", tree_reuse=True)
+    # oth_search_advance on an engine without reuse is an error
+    eng = pkg.SearchEngine(4, 4, search="alphazero")
+    s0, o0 = sr.start_position(8)
+    _, batch = rr.evaluator("stub", 8)
+    eng.search_begin([s0] * 2, [o0] * 2)
+    feed(eng, batch)
+    with pytest.raises(pkg._lib.OthelloHipError, match="tree_reuse"):
+        eng.search_advance([19, 19])
+    assert eng.reuse_stats()["inherited_roots"] == 0
+    # tree_reuse=False is the engine without the keyword
+    torch.manual_seed(3)
+    net = pkg.OthelloResNet(2, 16).eval()
+    ev = pkg.HipResNetEvaluator(net)
+    out = []
+    for more in ({}, {"tree_reuse": False}):
+        for search in ("alphazero", "reference"):
+            e = pkg.SearchEngine(8, 6, temperature_threshold=8, evaluator=ev, rules="othello", search=search, **more)
+            out.append(e.selfplay_fetch(e.selfplay_run(8, 41)))
+            assert e.counters()["simulations"] == e.counters()["plies"] * 6
+    for a, b in zip(out[0] + out[1], out[2] + out[3]):
+        assert np.array_equal(a, b)
