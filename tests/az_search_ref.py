@@ -1,67 +1,23 @@
 """Independent definitions for the search-semantics tests (test infrastructure only; nothing under the package imports this).
 
-``py_search_az``   -- one position's PUCT search under the AlphaZero semantics (``search="alphazero"``), on the package's
-                      own ``node.MCTSNode`` and the rules objects of std_rules_ref: the root counts itself once plus
-                      every simulation, and the value is negated BEFORE each update on the way up, so a child holds the
-                      value from the view of the side that chose it.  Everything else is std_rules_ref.py_search.
+``py_search_az``   -- one position's PUCT search under the AlphaZero semantics (``search="alphazero"``):
+                      std_rules_ref.py_search with semantics="alphazero" -- the root counts itself once plus every
+                      simulation, and the value is negated BEFORE each update on the way up, so a child holds the value
+                      from the view of the side that chose it.
 ``dirichlet_ref``  -- the root noise of the device restated in numpy float64 from its specification: Philox4x32-10,
                       counter (c0, c1, 0x44495249 + attempt words, child rank), Marsaglia-Tsang gamma variates, normalised.
 """
 import numpy as np
 
 import std_rules_ref as sr
-from othello_reinforcement_learning_test_amd.node import MCTSNode
 
 U64 = np.uint64
 NOISE_WORD = 0x44495249
 
 
 def py_search_az(rules, s, o, sims, c_puct, eval_fn, root_prior=None):
-    """-> (visits int32, value_sum float64, prior float32, pi float32 at temperature 1), each of length n*n+1.
-    root_prior (length n*n+1): overwrites the priors of the root's children (noisy priors read back from the device)."""
-    npol = rules.n * rules.n + 1
-    root = MCTSNode(prior=1.0)
-    root.visit_count = 1
-    probs, _ = eval_fn(s, o, rules.legal(s, o))
-    root.expand(np.asarray(probs, dtype=np.float32), sr.legal_actions(rules, s, o))
-    if root_prior is not None:
-        for a, ch in root.children.items():
-            ch.prior = np.float32(root_prior[a])
-    for _ in range(sims):
-        node, cs, co, path = root, s, o, []
-        while True:
-            action, child = node.select_child(c_puct)
-            cs, co = sr.apply_move(rules, cs, co, action)
-            path.append(child)
-            if child.is_leaf():
-                break
-            node = child
-        lg = rules.legal(cs, co)
-        if lg == 0 and rules.legal(co, cs) == 0:
-            ds = sr.popcount(cs) - sr.popcount(co)
-            value = float((ds > 0) - (ds < 0))          # relative to the side to move at the leaf
-        else:
-            probs, v = eval_fn(cs, co, lg)
-            path[-1].expand(np.asarray(probs, dtype=np.float32), sr.legal_actions(rules, cs, co))
-            value = float(np.float32(v))
-        for nd in reversed(path):
-            value = -value
-            nd.update(value)
-        root.visit_count += 1
-    visits = np.zeros(npol, dtype=np.int32)
-    wsum = np.zeros(npol, dtype=np.float64)
-    prior = np.zeros(npol, dtype=np.float32)
-    pi = np.zeros(npol, dtype=np.float32)
-    actions = list(root.children)
-    for a in actions:
-        ch = root.children[a]
-        visits[a], wsum[a], prior[a] = ch.visit_count, ch.value_sum, ch.prior
-    counts = np.array([root.children[a].visit_count for a in actions], dtype=np.float32)
-    if counts.any():
-        counts /= counts.sum()
-        for a, p in zip(actions, counts):
-            pi[a] = p
-    return visits, wsum, prior, pi
+    """-> the rows of sr.py_search.  root_prior: the noisy priors of the root's children, read back from the device."""
+    return sr.py_search(rules, s, o, sims, c_puct, eval_fn, "alphazero", root_prior)
 
 
 def winner_of(s, o):

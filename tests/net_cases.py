@@ -2,6 +2,7 @@
 tests/test_gpu_net_contract.py runs every trunk build on them): the networks, the inputs and the float64 reference, all
 deterministic functions of seeds.  Nothing here touches the GPU or the native library: `pkg` is anything with an
 ``OthelloResNet`` attribute (the package on the GPU box; `torch_only_pkg()` where the library may not be built)."""
+import hashlib
 import os
 import types
 
@@ -176,3 +177,28 @@ def reference(pkg, net, x, device="cpu"):
         tl, tv = net64(x.double())
     return {"rl": rl, "rv": rv, "tl": tl, "tv": tv, "amax": amax,
             "noise_l": (rl.double() - tl).abs().max().item(), "noise_v": (rv.double() - tv).abs().max().item()}
+
+
+# ---------------------------------------------------------------------------------------------- the widths fixture
+# the nets of tests/golden/g10_net_widths.npz (tests/test_net_widths_cpu.py on the CPU, tests/test_gpu_net_widths.py on the HIP trunks)
+WIDTH_NETS = {8: ((2, 48), (3, 96), (2, 160), (2, 192), (4, 256)), 6: ((2, 96), (2, 176), (2, 256))}
+
+
+def widths_inputs(golden, board):
+    """(N,3,S,S) float32 inputs of the fixture's nets: g4's 32 positions on 8x8, g7's planes on 6x6"""
+    if board == 8:
+        import oracle_lib as ol
+        return torch.from_numpy(np.stack([ol.tensor(ol.board(s, o)) for s, o in golden("g4_net.npz")["pos"]]))
+    return torch.from_numpy(golden("g7_net6.npz")["x"])
+
+
+def widths_net(pkg, g, board, seed, nb, nf):
+    """the package's seeded net, checked against the fixture's key names and hashes -> (tag, net)"""
+    tag = "b%d_s%d_%dx%d" % (board, seed, nb, nf)
+    torch.manual_seed(seed)
+    net = pkg.OthelloResNet(nb, nf, board_size=board).eval()
+    sd = net.state_dict()
+    assert list(sd.keys()) == list(g[tag + "_keys"])
+    for k, h in zip(g[tag + "_keys"], g[tag + "_sha"]):
+        assert hashlib.sha256(sd[k].numpy().tobytes()).hexdigest() == h, (tag, k)
+    return tag, net

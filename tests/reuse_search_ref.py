@@ -6,7 +6,8 @@
                          expanded; otherwise (an unvisited move) the next search starts from a fresh root;
                        * budget = top-up: a search ends when the root's children hold ``sims`` visits, so an inherited
                          root with V0 visits runs sims - V0 new simulations and a fresh root runs sims;
-                       * ``root_prior`` overrides the priors of the root's children (noisy priors), as in py_search_az.
+                       * ``root_prior`` overrides the priors of the root's children (noisy priors), as in py_search_az;
+                       * a simulation and the root's rows are std_rules_ref's (``simulate`` under "alphazero", ``root_rows``).
 ``flatten``          a tree as the device's arena (node ids and edge bases in expansion order).
 ``compact_in_place`` a numpy model of k_reroot's in-place compaction of such an arena.
 ``scripted_games``   the scripted inputs shared by the CPU condition test and the GPU tests: whole games, moves mostly the
@@ -22,7 +23,8 @@ U64 = np.uint64
 
 class ReuseSearch:
     def __init__(self, rules, sims, c_puct, eval_fn):
-        self.rules, self.sims, self.c_puct, self.eval_fn = rules, int(sims), c_puct, eval_fn
+        self.rules, self.sims, self.c_puct = rules, int(sims), c_puct
+        self._plain_expand = sr.plain_expand(rules, eval_fn)
         self.npol = rules.n * rules.n + 1
         self.root = None
         self.pos = None
@@ -30,8 +32,8 @@ class ReuseSearch:
 
     # -- tree building --------------------------------------------------------------------------------------------
     def _expand(self, node, s, o):
-        probs, v = self.eval_fn(s, o, self.rules.legal(s, o))
-        node.expand(np.asarray(probs, dtype=np.float32), sr.legal_actions(self.rules, s, o))
+        """The expand hook of sr.simulate that also stamps the node with its position and its expansion rank."""
+        v = self._plain_expand(node, s, o)
         node.pos = (s, o)
         node.order = self._order
         self._order += 1
@@ -54,47 +56,15 @@ class ReuseSearch:
 
     def top_up(self):
         """Run simulations until the root's children hold `sims` visits.  -> (V0, number of new simulations)."""
-        root, rules = self.root, self.rules
         v0 = self.v0()
         new = max(0, self.sims - v0)
         for _ in range(new):
-            node, (cs, co), path = root, self.pos, []
-            while True:
-                action, child = node.select_child(self.c_puct)
-                cs, co = sr.apply_move(rules, cs, co, action)
-                path.append(child)
-                if child.is_leaf():
-                    break
-                node = child
-            lg = rules.legal(cs, co)
-            if lg == 0 and rules.legal(co, cs) == 0:
-                ds = sr.popcount(cs) - sr.popcount(co)
-                value = float((ds > 0) - (ds < 0))          # relative to the side to move at the leaf
-            else:
-                value = float(np.float32(self._expand(path[-1], cs, co)))
-            for nd in reversed(path):
-                value = -value
-                nd.update(value)
-            root.visit_count += 1
+            sr.simulate(self.rules, self.root, *self.pos, self.c_puct, self._expand, "alphazero")
         return v0, new
 
     def results(self):
         """-> (visits int32, value_sum float64, prior float32, pi float32 at temperature 1) of the root's children."""
-        npol = self.npol
-        visits = np.zeros(npol, dtype=np.int32)
-        wsum = np.zeros(npol, dtype=np.float64)
-        prior = np.zeros(npol, dtype=np.float32)
-        pi = np.zeros(npol, dtype=np.float32)
-        actions = list(self.root.children)
-        for a in actions:
-            ch = self.root.children[a]
-            visits[a], wsum[a], prior[a] = ch.visit_count, ch.value_sum, ch.prior
-        counts = np.array([self.root.children[a].visit_count for a in actions], dtype=np.float32)
-        if counts.any():
-            counts /= counts.sum()
-            for a, p in zip(actions, counts):
-                pi[a] = p
-        return visits, wsum, prior, pi
+        return sr.root_rows(self.root, self.npol)
 
     def advance(self, action):
         """Play `action` from the root.  -> "over" (the successor is terminal: no root), "inherited" (the child's subtree is
@@ -205,8 +175,7 @@ def arenas_equal(x, y):
 
 
 # ---------------------------------------------------------------------------------------------- scripted games
-def rules_obj(bs, name):
-    return sr.RayRules(bs) if name == "othello" else sr.MaskRules(bs, swapped=True)
+rules_obj = sr.rules_obj
 
 
 def evaluator(family, bs):

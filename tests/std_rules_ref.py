@@ -6,9 +6,11 @@
                   masks, or the unswapped ones): used to run the Python search under the reference's game, where the C
                   oracle can check it.
 ``py_search``  -- one position's PUCT search on the package's own ``node.MCTSNode`` (the reference's node arithmetic),
-                  with the rules as a parameter.  Trees of different games are independent and the evaluator is a pure
-                  function of the position, so the engine's lock-step schedule (one leaf per game per simulation)
-                  gives each game exactly this tree.
+                  with the rules and the search semantics as parameters.  Trees of different games are independent and
+                  the evaluator is a pure function of the position, so the engine's lock-step schedule (one leaf per
+                  game per simulation) gives each game exactly this tree.  It is ``simulate`` (one simulation) in a loop
+                  and ``root_rows`` (the root's statistics): the one definition of either in the tests, which
+                  az_search_ref.py_search_az and reuse_search_ref.ReuseSearch are built from too.
 Positions travel as (self, opp) integers with bit i = row * N + col, like everywhere else in the project.
 """
 import ctypes as C
@@ -178,35 +180,62 @@ def popcount(x):
     return bin(x).count("1")
 
 
-def py_search(rules, s, o, sims, c_puct, eval_fn):
-    """PUCT search of one position: mcts.py:100-168 / parallel_self_play.py:106-204 on MCTSNode.  eval_fn(self, opp, legal)
-    -> (probs float32[n*n+1], value).  The root is expanded and never backed up; a terminal leaf is backed up with the
-    winner at once and stays a leaf; values alternate sign from the leaf upwards.
-    -> (visits int32, value_sum float64, prior float32, pi float32 at temperature 1), each of length n*n+1."""
-    npol = rules.n * rules.n + 1
-    root = MCTSNode(prior=1.0)
-    probs, _ = eval_fn(s, o, rules.legal(s, o))
-    root.expand(np.asarray(probs, dtype=np.float32), legal_actions(rules, s, o))
-    for _ in range(sims):
-        node, cs, co, path = root, s, o, []
-        while True:
-            action, child = node.select_child(c_puct)
-            cs, co = apply_move(rules, cs, co, action)
-            path.append(child)
-            if child.is_leaf():
-                break
-            node = child
-        lg = rules.legal(cs, co)
-        if lg == 0 and rules.legal(co, cs) == 0:
-            ds = popcount(cs) - popcount(co)
-            value = float((ds > 0) - (ds < 0))
-        else:
-            probs, v = eval_fn(cs, co, lg)
-            path[-1].expand(np.asarray(probs, dtype=np.float32), legal_actions(rules, cs, co))
-            value = float(np.float32(v))
-        for nd in reversed(path):
-            nd.update(value)
-            value = -value
+_RULES = {}
+
+
+def rules_obj(bs, name):
+    """The Python rules of a rule set: the ray walk for standard Othello, the swapped shift-and-mask for the reference's.
+    One object per (board, rule set): its memo of legal masks is shared by every search that asks for it."""
+    if (bs, name) not in _RULES:
+        _RULES[(bs, name)] = RayRules(bs) if name == "othello" else MaskRules(bs, swapped=True)
+    return _RULES[(bs, name)]
+
+
+SEMANTICS = ("reference", "alphazero")
+
+
+def plain_expand(rules, eval_fn):
+    """The expand hook of `simulate` that only expands: hook(node, self, opp) evaluates the position, gives `node` its
+    children and returns the value."""
+    def expand(node, s, o):
+        probs, v = eval_fn(s, o, rules.legal(s, o))
+        node.expand(np.asarray(probs, dtype=np.float32), legal_actions(rules, s, o))
+        return v
+    return expand
+
+
+def simulate(rules, root, s, o, c_puct, expand, semantics):
+    """One simulation from `root`, an expanded MCTSNode that holds the position (s, o): descend with select_child to a
+    leaf; a terminal leaf is backed up with the winner at once and stays a leaf, any other is expanded through
+    expand(node, self, opp) -> value; the value, relative to the side to move at the leaf, alternates sign from the leaf
+    upwards.  "reference": the leaf is updated with the value as it is, and the root is never backed up.  "alphazero": the
+    value is negated BEFORE each update, so a child holds the value from the view of the side that chose it, and the root
+    counts the simulation."""
+    node, path = root, []
+    while True:
+        action, child = node.select_child(c_puct)
+        s, o = apply_move(rules, s, o, action)
+        path.append(child)
+        if child.is_leaf():
+            break
+        node = child
+    if rules.legal(s, o) == 0 and rules.legal(o, s) == 0:
+        ds = popcount(s) - popcount(o)
+        value = float((ds > 0) - (ds < 0))
+    else:
+        value = float(np.float32(expand(path[-1], s, o)))
+    if semantics == "alphazero":
+        value = -value
+    for nd in reversed(path):
+        nd.update(value)
+        value = -value
+    if semantics == "alphazero":
+        root.visit_count += 1
+
+
+def root_rows(root, npol):
+    """The statistics of the root's children.
+    -> (visits int32, value_sum float64, prior float32, pi float32 at temperature 1), each of length npol."""
     visits = np.zeros(npol, dtype=np.int32)
     wsum = np.zeros(npol, dtype=np.float64)
     prior = np.zeros(npol, dtype=np.float32)
@@ -217,11 +246,29 @@ def py_search(rules, s, o, sims, c_puct, eval_fn):
         visits[a], wsum[a], prior[a] = ch.visit_count, ch.value_sum, ch.prior
     counts = np.array([root.children[a].visit_count for a in actions], dtype=np.float32)   # node.py:162-177, T = 1
     if counts.any():
-        counts = counts ** (1.0 / 1.0)
         counts /= counts.sum()
         for a, p in zip(actions, counts):
             pi[a] = p
     return visits, wsum, prior, pi
+
+
+def py_search(rules, s, o, sims, c_puct, eval_fn, semantics="reference", root_prior=None):
+    """PUCT search of one position: mcts.py:100-168 / parallel_self_play.py:106-204 on MCTSNode.  eval_fn(self, opp, legal)
+    -> (probs float32[n*n+1], value).  semantics: see `simulate`; under "alphazero" the root also counts itself once.
+    root_prior (length n*n+1): overwrites the priors of the root's children (noisy priors read back from the device).
+    -> the root_rows."""
+    assert semantics in SEMANTICS
+    expand = plain_expand(rules, eval_fn)
+    root = MCTSNode(prior=1.0)
+    if semantics == "alphazero":
+        root.visit_count = 1
+    expand(root, s, o)
+    if root_prior is not None:
+        for a, ch in root.children.items():
+            ch.prior = np.float32(root_prior[a])
+    for _ in range(sims):
+        simulate(rules, root, s, o, c_puct, expand, semantics)
+    return root_rows(root, rules.n * rules.n + 1)
 
 
 # ---------------------------------------------------------------------------------------------- the library's host ABI

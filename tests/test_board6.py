@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib6 as o6
+from gpu_support import dev_u64
 from stub_eval import stub_probs_values
 
 U64 = np.uint64
@@ -94,11 +95,6 @@ def pkg():
     import othello_reinforcement_learning_test_amd as p
     p._lib.require_device()
     return p
-
-
-def dev_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
 
 
 @pytest.mark.gpu

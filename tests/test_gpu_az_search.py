@@ -9,14 +9,15 @@ import torch
 
 import az_search_ref as az
 import oracle_lib as ol
+import reuse_search_ref as rr
 import search_cases as sc
 import std_rules_ref as sr
+from gpu_support import (assert_rows_equal, check_stream, hip_eval_fn, lockstep_selfplay, pi_checked_move, roots_of, split,
+                         stream_of, stub_host_eval, want_search)
 from stub_eval import stub_probs_values
 
 pytestmark = pytest.mark.gpu
-U64 = np.uint64
 F32 = np.float32
-REF, STD = 0, 1
 
 
 @pytest.fixture(scope="module")
@@ -26,69 +27,15 @@ def pkg():
     return p
 
 
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def bits_of(planes):
-    w = U64(1) << np.arange(planes.shape[1], dtype=U64)
-    return (planes.astype(U64) * w[None, :]).sum(axis=1, dtype=U64)
-
-
-_RULES = {}
-
-
-def rules_obj(bs, name):
-    """The Python rules of a rule set: the ray walk for standard Othello, the swapped shift-and-mask for the reference's."""
-    if (bs, name) not in _RULES:
-        _RULES[(bs, name)] = sr.RayRules(bs) if name == "othello" else sr.MaskRules(bs, swapped=True)
-    return _RULES[(bs, name)]
-
-
-def stub_host_eval(npol):
-    table = sr.stub_table()
-    return lambda s, o, lg: stub_probs_values(s, o, table, npol)
-
-
-def roots_of(bs, name, n=64):
-    return sr.search_roots(bs, STD if name == "othello" else REF, n)
-
-
-def split(roots):
-    return [r[0] for r in roots], [r[1] for r in roots]
-
-
 # ---- 1. the search, bit for bit ----------------------------------------------------------------------------------------
-_WANT = {}
-
-
-def want_search(bs, name, sims, cp):
-    """py_search_az of the 64 roots of (board, rule set), computed once per (board, rules, sims, c_puct)."""
-    key = (bs, name, sims, cp)
-    if key not in _WANT:
-        fn = sr.stub_eval_fn(bs * bs + 1)
-        roots = roots_of(bs, name)
-        _WANT[key] = (roots, [az.py_search_az(rules_obj(bs, name), s, o, sims, cp, fn) for s, o in roots])
-    return _WANT[key]
-
-
-def assert_rows_equal(got, want, what=""):
-    pi, visits, wsum, prior = got
-    for i, (wv, ww, wp, wpi) in enumerate(want):
-        assert np.array_equal(visits[i], wv), "%svisits of root %d" % (what, i)
-        assert np.array_equal(wsum[i], ww), "%svalue sums of root %d" % (what, i)
-        assert np.array_equal(prior[i], wp), "%spriors of root %d" % (what, i)
-        assert np.array_equal(pi[i], wpi), "%spi of root %d" % (what, i)
-
-
 @pytest.mark.parametrize("name", ["othello", "reference"])
 @pytest.mark.parametrize("cp", [1.0, 1.5])
 @pytest.mark.parametrize("sims", [5, 50])
 @pytest.mark.parametrize("n", [5, 64])
 @pytest.mark.parametrize("bs", [8, 6])
 def test_search_alphazero_equals_the_python_search(pkg, bs, n, sims, cp, name):
-    roots, want = want_search(bs, name, sims, cp)
-    rules = rules_obj(bs, name)
+    roots, want = want_search(bs, name, sims, cp, "alphazero")
+    rules = sr.rules_obj(bs, name)
     assert rules.legal(*roots[0]) == 0 and rules.legal(roots[0][1], roots[0][0]) != 0      # a root that must pass
     assert rules.legal(*roots[1]) == 0 and rules.legal(roots[1][1], roots[1][0]) == 0      # a terminal root
     eng = pkg.SearchEngine(n, sims, c_puct=cp, board_size=bs, rules=name, search="alphazero")
@@ -98,23 +45,14 @@ def test_search_alphazero_equals_the_python_search(pkg, bs, n, sims, cp, name):
     assert int(got[1].sum()) == n * sims       # (a terminal root's simulations all go through its pass child)
 
 
-def family_fns(name):
-    one = sc.engine_fn(name)
-
-    def fn(s, o, lg):
-        p, v = one(np.array([s], dtype=U64), np.array([o], dtype=U64), None)
-        return p[0], v[0]
-    return one, fn
-
-
 def test_search_alphazero_300_simulations_deep_lines_and_ties(pkg):
     """`onehot`: one prior 1, the rest 0 -- a single deep line with terminal back-ups; `ties`: equal priors and values in
     {-1, 0, +1} -- the descent is decided by the ballot's first maximum.  The reference's rules (the families' legality)."""
-    rules = rules_obj(8, "reference")
+    rules = sr.rules_obj(8, "reference")
     deep = [(s, o) for s, o, _ in sc.mid_game_positions(3)]
     late = [(s, o) for s, o, ply in sc.pick_positions(8) if ply >= 50][:5]
     for fam, roots in (("onehot", deep + late), ("ties", late + deep[:1])):
-        batch_fn, fn = family_fns(fam)
+        fn, batch_fn = rr.evaluator(fam, 8)
         eng = pkg.SearchEngine(len(roots), 300, c_puct=1.0, rules="reference", search="alphazero")
         got = eng.search_with(*split(roots), batch_fn)
         assert_rows_equal(got, [az.py_search_az(rules, s, o, 300, 1.0, fn) for s, o in roots], fam + ": ")
@@ -125,7 +63,7 @@ def test_search_alphazero_300_simulations_deep_lines_and_ties(pkg):
 def test_backup_sign_on_the_device(pkg):
     """A root child whose position ends the game is re-evaluated at every visit with winner(child), relative to the side to
     move at the child: under "alphazero" the child holds -winner, under "reference" +winner."""
-    rules = rules_obj(8, "reference")
+    rules = sr.rules_obj(8, "reference")
     pos = sc.game_positions(6, 77)
     roots = [(p[0], p[1]) for p, q in zip(pos, pos[1:] + [(0, 0, 0)]) if q[2] < p[2]]     # the last position of each game
     assert len(roots) == 6
@@ -208,7 +146,7 @@ def noise_runs(pkg):
 
 def test_root_noise_equals_the_restatement(pkg):
     r = noise_runs(pkg)
-    rules = rules_obj(8, "othello")
+    rules = sr.rules_obj(8, "othello")
     plain, noisy = r["plain"][3], r["noisy"][3]
     worst = 0.0
     for i, (s, o) in enumerate(r["roots"]):
@@ -241,7 +179,7 @@ def test_root_noise_equals_the_restatement(pkg):
 def test_root_noise_reaches_the_search(pkg):
     """The device's own noisy root priors handed to the Python search: the rest of the search is bit for bit the same."""
     r = noise_runs(pkg)
-    rules = rules_obj(8, "othello")
+    rules = sr.rules_obj(8, "othello")
     fn = sr.stub_eval_fn(65)
     pi, visits, wsum, prior = r["noisy"]
     for i, (s, o) in enumerate(r["roots"]):
@@ -263,102 +201,21 @@ def test_reference_semantics_ignore_the_noise(pkg):
 
 
 # ---- 5. lock-step self-play ------------------------------------------------------------------------------------------------
-def hip_eval_fn(ev, cap, bs):
-    """eval_fn of the Python searches whose answers are the HIP network's own: one position in a launch of `cap` rows (the
-    shape the engine launches), priors through oth_policy_exp (the engine's expf).  Memoised per position."""
-    memo = {}
-
-    def fn(s, o, lg):
-        if (s, o) not in memo:
-            ss, oo, ll = (np.zeros(cap, dtype=U64) for _ in range(3))
-            ss[0], oo[0], ll[0] = s, o, lg
-            logp, v = ev.forward_bits(dev_u64(ss), dev_u64(oo), dev_u64(ll))
-            memo[(s, o)] = (ev.policy_probs(logp)[0].cpu().numpy(), float(v[0, 0].cpu()))
-        return memo[(s, o)]
-    return fn
-
-
 def test_lockstep_selfplay_pi_equals_the_python_search(pkg):
     torch.manual_seed(8)
     net = pkg.OthelloResNet(2, 16).eval()
     ev = pkg.HipResNetEvaluator(net)
     sims, games = 6, 4
     eng = pkg.SearchEngine(games, sims, temperature_threshold=8, evaluator=ev, rules="othello", search="alphazero")
-    rules = rules_obj(8, "othello")
-    fn = hip_eval_fn(ev, games, 8)
-    pos = [sr.start_position(8)] * games
-    over, plies = [False] * games, [0] * games
-    rng = np.random.Generator(np.random.PCG64(2))
-    eng.selfplay_begin(games)
-    for ply in range(128):                               # whole games (the engine's own bound on the plies of a game)
-        if all(over):
-            break
-        pi, active = eng.selfplay_search()
-        assert active.tolist() == [0 if f else 1 for f in over]
-        actions = np.zeros(games, dtype=np.int32)
-        for i, (s, o) in enumerate(pos):
-            if over[i]:
-                continue
-            _, _, _, want = az.py_search_az(rules, s, o, sims, 1.0, fn)
-            assert np.array_equal(pi[i], want), "game %d ply %d" % (i, ply)
-            moves = np.flatnonzero(pi[i] > 0)            # different games take different lines
-            a = int(moves[int(rng.integers(len(moves)))])
-            assert a in sr.legal_actions(rules, s, o)
-            actions[i], plies[i] = a, plies[i] + 1
-            pos[i] = s, o = sr.apply_move(rules, s, o, a)
-            over[i] = rules.legal(s, o) == 0 and rules.legal(o, s) == 0
-        assert eng.selfplay_apply(actions) == over.count(False)
-    assert all(over)
-    n = eng.selfplay_end()
-    st, p, z, gl = eng.selfplay_fetch(n)
-    assert gl.tolist() == plies and n == sum(plies)
-    check_stream_az(8, "othello", st, p, z, games, gl)
+    rules = sr.rules_obj(8, "othello")
+    choose = pi_checked_move(rules, sims, hip_eval_fn(ev, games, 8), "alphazero", np.random.Generator(np.random.PCG64(2)))
+    got = lockstep_selfplay(eng, rules, games, 128, choose)    # whole games (the engine's own bound on the plies of a game)
+    assert all(got["over"])
+    assert got["gl"].tolist() == got["plies"] and got["n"] == sum(got["plies"])
+    check_stream(8, "othello", *got["tuples"], games, got["gl"], z="alphazero")
 
 
 # ---- 6. self-play streams and z ----------------------------------------------------------------------------------------------
-def check_stream_az(bs, name, states, pis, zs, n_games, game_len=None):
-    """Replay every game of a self-play stream with the Python rules: recorded positions are not terminal, plane 2 is the
-    legal mask, pi lives on the legal moves and sums to 1, a move of positive pi links each position to the next, the last
-    move ends the game, and z[t] = sign(own - opponent's discs at the end) from the view of the side to move at ply t.
-    -> the game lengths."""
-    rules = rules_obj(bs, name)
-    cells = bs * bs
-    s0, o0 = sr.start_position(bs)
-    st = states.reshape(len(states), 3, cells)
-    assert set(np.unique(st)) <= {0.0, 1.0}
-    sb, ob, lb = (bits_of(st[:, j]) for j in range(3))
-    starts = [i for i in range(len(zs)) if (int(sb[i]), int(ob[i])) == (s0, o0)]
-    assert len(starts) == n_games, "games in the stream"
-    bounds = starts + [len(zs)]
-    lens = [bounds[g + 1] - bounds[g] for g in range(n_games)]
-    if game_len is not None:
-        assert lens == list(game_len)
-    for g in range(n_games):
-        lo, hi = bounds[g], bounds[g + 1]
-        ends = []
-        for t in range(lo, hi):
-            s, o = int(sb[t]), int(ob[t])
-            lg = rules.legal(s, o)
-            assert int(lb[t]) == lg, "plane 2 is the legal mask"
-            assert not (lg == 0 and rules.legal(o, s) == 0), "a recorded position is not terminal"
-            legal = sr.legal_actions(rules, s, o)
-            pi = pis[t]
-            assert all(pi[a] == 0 for a in range(cells + 1) if a not in legal), "pi is zero off the legal set"
-            assert abs(float(pi.astype(np.float64).sum()) - 1.0) < 1e-6
-            succ = [sr.apply_move(rules, s, o, a) for a in legal if pi[a] > 0]
-            if t + 1 < hi:
-                assert (int(sb[t + 1]), int(ob[t + 1])) in succ, "game %d ply %d: no move leads to the next state" % (g, t - lo)
-            else:
-                ends = [(cs, co) for cs, co in succ if rules.legal(cs, co) == 0 and rules.legal(co, cs) == 0]
-                assert ends, "game %d: its last move does not end the game" % g
-        n = hi - lo
-        # the side to move at the end is the mover of ply p exactly when n - p is even (the sides alternate every ply)
-        wants = [np.array([az.winner_of(cs, co) * (1.0 if (n - p) % 2 == 0 else -1.0) for p in range(n)], dtype=F32)
-                 for cs, co in ends]
-        assert any(np.array_equal(zs[lo:hi], w) for w in wants), "game %d (%d plies): z" % (g, n)
-    return lens
-
-
 @pytest.mark.parametrize("bs,name", [(8, "othello"), (6, "reference")])
 def test_device_rng_selfplay_and_z(pkg, bs, name):
     torch.manual_seed(3)
@@ -369,7 +226,7 @@ def test_device_rng_selfplay_and_z(pkg, bs, name):
     n = eng.selfplay_run(8, 41, add_noise=False)
     st, pi, z, gl = eng.selfplay_fetch(n)
     assert n == gl.sum()
-    lens = check_stream_az(bs, name, st, pi, z, 8, gl)
+    lens, _ = check_stream(bs, name, st, pi, z, 8, gl, z="alphazero")
     print("game lengths:", lens)
     # the reference's formula (winner x +1 on even plies) has the wrong sign in exactly the games of odd length
     assert any(m % 2 == 1 for m in lens), "no game of odd length among the seeded games"
@@ -393,7 +250,7 @@ def test_noise_in_selfplay(pkg):
     for a, b in zip(noisy, again):
         assert np.array_equal(a, b)
     assert not (noisy[1].shape == plain[1].shape and np.array_equal(noisy[1], plain[1]))
-    check_stream_az(8, "othello", *noisy[:3], 8, noisy[3])
+    check_stream(8, "othello", *noisy[:3], 8, noisy[3], z="alphazero")
     cached = run(True, eval_cache_log2=4)            # the cache holds raw network rows: the noise is applied after it
     for a, b in zip(cached, noisy):
         assert np.array_equal(a, b)
@@ -406,10 +263,6 @@ def test_noise_in_selfplay(pkg):
         assert np.array_equal(a, b)
 
 
-def stream_of(data):
-    return (np.stack([d[0] for d in data]), np.stack([d[1] for d in data]), np.array([d[2] for d in data], dtype=F32))
-
-
 def test_workers(pkg):
     torch.manual_seed(5)
     net = pkg.OthelloResNet(2, 16).eval()
@@ -418,21 +271,21 @@ def test_workers(pkg):
                                    num_parallel_games=8, verbose=False, lanes=2, search="alphazero")
     assert w.search == "alphazero" and w.engine.search == "alphazero" and w.batch_mcts.search == "alphazero"
     assert [e.search for e in w._lane_engines] == ["alphazero"] * 2 and [e.rules for e in w._lane_engines] == ["othello"] * 2
-    check_stream_az(8, "othello", *stream_of(w.execute_episodes(8, add_dirichlet_noise=True)), 8)
+    check_stream(8, "othello", *stream_of(w.execute_episodes(8, add_dirichlet_noise=True)), 8, z="alphazero")
     assert w._ran is w._lane_engines
     assert w.last_stats["search"] == "alphazero" and w.last_stats["rules"] == "othello"
     # one lane, and a call wide enough to grow the engine: the grown engine keeps both settings
     q = pkg.ParallelSelfPlayWorker(pkg.OthelloBitboard, net, num_simulations=6, temperature_threshold=8,
                                    num_parallel_games=4, verbose=False, lanes=1, search="alphazero")
     first = q.engine
-    check_stream_az(8, "reference", *stream_of(q.execute_episodes(8, add_dirichlet_noise=False)), 8)
+    check_stream(8, "reference", *stream_of(q.execute_episodes(8, add_dirichlet_noise=False)), 8, z="alphazero")
     assert q.engine is not first and q.engine.search == "alphazero" and q.engine.rules == "reference"
     assert q.last_stats["search"] == "alphazero" and q.last_stats["rules"] == "reference"
     # the serial worker follows its MCTS object; root_value is no longer the constant 0.0
     mcts = pkg.MCTS(net, search="alphazero")
     sw = pkg.SelfPlayWorker(pkg.StandardOthelloBitboard, mcts, num_simulations=6, temperature_threshold=8)
     assert sw.search == "alphazero"
-    check_stream_az(8, "othello", *stream_of(sw.execute_episodes(5)), 5)
+    check_stream(8, "othello", *stream_of(sw.execute_episodes(5)), 5, z="alphazero")
     assert sw._engine.search == "alphazero"
     b = pkg.StandardOthelloBitboard()
     np.random.seed(1)

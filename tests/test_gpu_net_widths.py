@@ -14,8 +14,7 @@ import torch
 
 import net_cases as nc
 import oracle_lib as ol
-from test_gpu_selfplay_exact import assert_streams_equal, dev_u64, hip_net_eval
-from test_net_widths_cpu import NETS, widths_inputs, widths_net
+from gpu_support import assert_streams_equal, dev_u64, hip_net_eval
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
@@ -138,10 +137,10 @@ def test_reference_outputs_at_new_widths(pkg, golden, board, seed):
     """Every net of g10_net_widths.npz: weights regenerated from the seed and checked by hash, HIP outputs within 1e-4 of what
     the reference's own module returned."""
     g = golden("g10_net_widths.npz")
-    x = widths_inputs(golden, board).cuda()
+    x = nc.widths_inputs(golden, board).cuda()
     with coop_env(None):
-        for nb, nf in NETS[board]:
-            tag, net = widths_net(pkg, g, board, seed, nb, nf)
+        for nb, nf in nc.WIDTH_NETS[board]:
+            tag, net = nc.widths_net(pkg, g, board, seed, nb, nf)
             ev = pkg.HipResNetEvaluator(net)
             assert ev.precision == "f32" and ev.kernel_info(len(x))["kernel"].startswith(dispatched_kernel(nf))
             logp, v = ev.forward_planes(x)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import oracle_lib as ol
+from gpu_support import dev_u64, host_u64
 from net_cases import _max_activation, _trained_like
 from stub_eval import stub_probs_values
 
@@ -21,14 +22,6 @@ def pkg():
     import othello_reinforcement_learning_test_amd as p
     p._lib.require_device()   # fail loudly, never skip: -m gpu means a GPU box
     return p
-
-
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host_u64(t):
-    return t.cpu().numpy().view(U64)
 
 
 def random_positions(n, seed):

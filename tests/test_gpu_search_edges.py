@@ -282,7 +282,7 @@ def test_selfplay_under_a_saturated_policy_head(pkg, regime):
     """A 2x16 network whose pass logit is raised by 200 / 95: log_softmax puts every legal move of a non-pass node at about
     -200 (expf = 0: the uniform fallback at every such node) / about -95 (denormal priors).  The whole device self-play
     (run_search's in-kernel expf, the sampling from pi, the refill) == the oracle driven by the HIP network's own outputs."""
-    from test_gpu_selfplay_exact import assert_streams_equal, hip_net_eval
+    from gpu_support import assert_streams_equal, hip_net_eval
     torch.manual_seed(321)
     net = pkg.OthelloResNet(2, 16).eval()
     with torch.no_grad():

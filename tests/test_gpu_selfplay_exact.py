@@ -10,10 +10,10 @@ import pytest
 import torch
 
 import oracle_lib as ol
+from gpu_support import assert_streams_equal, hip_net_eval, simulate_stream
 from stub_eval import stub_probs_values
 
 pytestmark = pytest.mark.gpu
-U64 = np.uint64
 
 
 @pytest.fixture(scope="module")
@@ -21,47 +21,6 @@ def pkg():
     import othello_reinforcement_learning_test_amd as p
     p._lib.require_device()
     return p
-
-
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def hip_net_eval(ev, cap, olib=None):
-    """orc_eval_fn whose answers are the HIP network's: oth_net_forward_bits on launches of `cap` rows (the shape
-    the engine launches, so the same kernel build runs) and oth_policy_exp (the engine's expf) for the priors.
-    olib: the oracle binding the callback is for (oracle_lib, or oracle_lib6 for a 6x6 network)."""
-    olib = olib or ol
-    calls = {"n": 0, "pos": 0}
-
-    def fn(s, o):
-        n = len(s)
-        probs = np.empty((n, olib.NPOL), dtype=np.float32)
-        vals = np.empty(n, dtype=np.float32)
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
-            ss, oo = np.zeros(cap, dtype=U64), np.zeros(cap, dtype=U64)
-            ss[:m], oo[:m] = s[i:i + m], o[i:i + m]
-            lg = olib.legal_batch(ss, oo)
-            logp, v = ev.forward_bits(dev_u64(ss), dev_u64(oo), dev_u64(lg))
-            probs[i:i + m] = ev.policy_probs(logp)[:m].cpu().numpy()
-            vals[i:i + m] = v[:m, 0].cpu().numpy()
-        calls["n"] += 1
-        calls["pos"] += n
-        return probs, vals
-    cb = olib.make_eval(fn)
-    cb.calls = calls
-    return cb
-
-
-def assert_streams_equal(got, want, what=""):
-    st, pi, z, gl = got
-    ws, wp, wz, wl = want
-    assert np.array_equal(gl, wl), "%s: game lengths differ: %s vs %s" % (what, gl[:16], wl[:16])
-    assert len(z) == len(wz)
-    assert np.array_equal(st, ws), "%s: states differ" % what
-    assert np.array_equal(pi, wp), "%s: pi differ" % what
-    assert np.array_equal(z, wz), "%s: z differ" % what
 
 
 CASES = [
@@ -145,43 +104,6 @@ def test_selfplay_lanes_exact(pkg, lanes, board, blocks, filters):
     assert off == len(data)
     # the lane check ran on this first multi-lane call (toy launches are launch-bound: measured, never flagged)
     assert w.last_stats["lanes_overlap"] is not None and w.last_stats["lanes_serialised"] is False
-
-
-def simulate_stream(lengths, slots, stagger, targets):
-    """The streaming schedule restated on the host from the oracle's game lengths: which game ids each step
-    returns.  Slot g starts game g at round g*stagger//slots; a finished slot takes the next id; a step ends with
-    the round after the one at which >= target games had finished since the last harvest (at least two rounds)."""
-    join = [(g * stagger) // slots for g in range(slots)]
-    playing = {}          # gid -> plies played
-    next_id = slots
-    for g in range(slots):
-        if join[g] == 0:
-            playing[g] = 0
-    rnd, done_total, harvested, steps = 0, [], 0, []
-    done_after = {0: 0}
-    for target in targets:
-        first = rnd + 1
-        while True:
-            rnd += 1
-            finished = []
-            for gid in list(playing):
-                playing[gid] += 1
-                if playing[gid] == lengths[gid]:
-                    finished.append(gid)
-                    del playing[gid]
-            for gid in finished:
-                done_total.append(gid)
-                playing[next_id] = 0
-                next_id += 1
-            for g in range(slots):
-                if join[g] == rnd:
-                    playing[g] = 0
-            done_after[rnd] = len(done_total)
-            if rnd > first and done_after[rnd - 1] - harvested >= target:
-                break
-        steps.append(sorted(done_total[harvested:]))
-        harvested = len(done_total)
-    return steps, next_id
 
 
 @pytest.mark.parametrize("stagger", [0, 7])

@@ -10,11 +10,12 @@ import torch
 
 import oracle_lib as ol
 import std_rules_ref as sr
+from gpu_support import (REF, STD, assert_rows_equal, bits_of, check_stream, dev_u64, hip_eval_fn, host_u64,
+                         lockstep_selfplay, pi_checked_move, split, stream_of, stub_host_eval, want_search)
 from stub_eval import stub_probs_values
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
-REF, STD = 0, 1
 
 
 @pytest.fixture(scope="module")
@@ -22,20 +23,6 @@ def pkg():
     import othello_reinforcement_learning_test_amd as p
     p._lib.require_device()
     return p
-
-
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host_u64(t):
-    return t.cpu().numpy().view(U64)
-
-
-def bits_of(planes):
-    """[n, cells] 0/1 -> uint64[n]"""
-    w = U64(1) << np.arange(planes.shape[1], dtype=U64)
-    return (planes.astype(U64) * w[None, :]).sum(axis=1, dtype=U64)
 
 
 def unpack(bits, cells):
@@ -191,45 +178,20 @@ def test_sym_perm_is_the_library_transform(pkg):
 
 
 # ---- 4. search -----------------------------------------------------------------------------------------------------
-_WANT = {}
-
-
-def want_search(bs, sims, cp):
-    """py_search of the 64 roots of a board size under standard rules (computed once per (board, sims, c_puct))."""
-    key = (bs, sims, cp)
-    if key not in _WANT:
-        rules = _WANT.setdefault(("rules", bs), sr.RayRules(bs))
-        fn = sr.stub_eval_fn(bs * bs + 1)
-        roots = sr.search_roots(bs, STD, 64)
-        _WANT[key] = (roots, [sr.py_search(rules, s, o, sims, cp, fn) for s, o in roots])
-    return _WANT[key]
-
-
-def stub_host_eval(npol):
-    table = sr.stub_table()
-    return lambda s, o, lg: stub_probs_values(s, o, table, npol)
-
-
 @pytest.mark.parametrize("cp", [1.0, 1.5])
 @pytest.mark.parametrize("sims", [5, 50])
 @pytest.mark.parametrize("n", [5, 64])
 @pytest.mark.parametrize("bs", [8, 6])
 def test_search_othello_equals_the_python_search(pkg, bs, n, sims, cp):
-    roots, want = want_search(bs, sims, cp)
-    rules = sr.RayRules(bs)
+    roots, want = want_search(bs, "othello", sims, cp, "reference")
+    rules = sr.rules_obj(bs, "othello")
     assert rules.legal(*roots[0]) == 0 and rules.legal(roots[0][1], roots[0][0]) != 0      # a root that must pass
     assert rules.legal(*roots[1]) == 0 and rules.legal(roots[1][1], roots[1][0]) == 0      # a terminal root
     eng = pkg.SearchEngine(n, sims, c_puct=cp, board_size=bs, rules="othello")
     assert eng.rules == "othello"
-    pi, visits, wsum, prior = eng.search_with([r[0] for r in roots[:n]], [r[1] for r in roots[:n]],
-                                              stub_host_eval(bs * bs + 1))
-    for i in range(n):
-        wv, ww, wp, wpi = want[i]
-        assert np.array_equal(visits[i], wv), "visits of root %d" % i
-        assert np.array_equal(wsum[i], ww), "value sums of root %d" % i
-        assert np.array_equal(prior[i], wp), "priors of root %d" % i
-        assert np.array_equal(pi[i], wpi), "pi of root %d" % i
-    assert int(visits.sum()) == n * sims
+    got = eng.search_with(*split(roots[:n]), stub_host_eval(bs * bs + 1))
+    assert_rows_equal(got, want[:n])
+    assert int(got[1].sum()) == n * sims
 
 
 @pytest.mark.parametrize("bs", [8, 6])
@@ -243,7 +205,7 @@ def test_search_at_rules_reference_still_equals_the_oracle(pkg, bs):
     table = sr.stub_table()
     ev = olib.make_eval(lambda s, o: stub_probs_values(s, o, table, npol))
     roots = sr.search_roots(bs, STD, 5)      # (any positions do: a passing and a terminal one under standard rules first)
-    sb, ob = [r[0] for r in roots], [r[1] for r in roots]
+    sb, ob = split(roots)
     a = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs, rules="reference").search_with(sb, ob, stub_host_eval(npol))
     b = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs).search_with(sb, ob, stub_host_eval(npol))
     c = pkg.SearchEngine(5, 50, c_puct=1.5, board_size=bs, rules="othello").search_with(sb, ob, stub_host_eval(npol))
@@ -257,52 +219,6 @@ def test_search_at_rules_reference_still_equals_the_oracle(pkg, bs):
 
 
 # ---- 5. self-play --------------------------------------------------------------------------------------------------
-def check_stream(bs, states, pis, zs, n_games, game_len=None):
-    """Replay every game of a self-play stream with the ray-walk board (see the checks in the issue's list)."""
-    cells = bs * bs
-    s0, o0 = sr.start_position(bs)
-    st = states.reshape(len(states), 3, cells)
-    assert set(np.unique(st)) <= {0.0, 1.0}
-    sb, ob, lb = (bits_of(st[:, j]) for j in range(3))
-    starts = [i for i in range(len(zs)) if (int(sb[i]), int(ob[i])) == (s0, o0)]
-    assert len(starts) == n_games, "games in the stream"
-    bounds = starts + [len(zs)]
-    if game_len is not None:
-        assert [bounds[g + 1] - bounds[g] for g in range(n_games)] == list(game_len)
-    passes = 0
-    for g in range(n_games):
-        lo, hi = bounds[g], bounds[g + 1]
-        winners = set()
-        for t in range(lo, hi):
-            s, o = int(sb[t]), int(ob[t])
-            rb = sr.RayBoard(bs, s, o)
-            lg = rb.legal()
-            assert int(lb[t]) == lg, "plane 2 is the standard legal mask"
-            assert not (lg == 0 and rb.legal(-1) == 0), "a recorded position is not terminal"
-            legal = [a for a in range(cells) if (lg >> a) & 1] or [cells]
-            passes += legal == [cells]
-            pi = pis[t]
-            assert all(pi[a] == 0 for a in range(cells + 1) if a not in legal), "pi is zero off the legal set"
-            assert abs(float(pi.astype(np.float64).sum()) - 1.0) < 1e-6
-            succ = {}
-            for a in legal:
-                if pi[a] > 0:
-                    nb = sr.RayBoard(bs, s, o)
-                    assert nb.make_move(a)
-                    succ[nb.bits()] = nb
-            if t + 1 < hi:      # linked to the next recorded state by a standard-legal move (or the pass) with pi > 0
-                assert (int(sb[t + 1]), int(ob[t + 1])) in succ, "game %d ply %d: no legal move leads to the next state" % (g, t - lo)
-            else:               # the last ply: the game ends exactly at a standard-terminal position
-                ends = [nb for nb in succ.values() if nb.is_terminal()]
-                assert ends, "game %d: its last move does not end the game" % g
-                winners = {nb.winner() for nb in ends}
-        # z = winner (relative to the side to move at the end) x (+1 on even plies, -1 on odd)   [L16]
-        z = zs[lo:hi]
-        sign = np.array([1.0 if (t - lo) % 2 == 0 else -1.0 for t in range(lo, hi)], dtype=np.float32)
-        assert any(np.array_equal(z, np.float32(w) * sign) for w in winners), "game %d: z" % g
-    return passes
-
-
 def test_selfplay_worker_on_standard_rules(pkg):
     torch.manual_seed(3)
     net = pkg.OthelloResNet(2, 16).eval()
@@ -312,10 +228,7 @@ def test_selfplay_worker_on_standard_rules(pkg):
     np.random.seed(5)
     data = w.execute_episodes(12)
     assert w.engine.rules == "othello"              # (the engine a 12-game call grows is on the same rules)
-    states = np.stack([d[0] for d in data])
-    pis = np.stack([d[1] for d in data])
-    zs = np.array([d[2] for d in data], dtype=np.float32)
-    check_stream(8, states, pis, zs, 12)
+    check_stream(8, "othello", *stream_of(data), 12)
     np.random.seed(5)
     again = w.execute_episodes(12)
     assert len(again) == len(data) and all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
@@ -333,10 +246,6 @@ def test_selfplay_worker_on_standard_rules(pkg):
     assert not (other[0].shape == want[0].shape and np.array_equal(other[0], want[0]))   # the rule sets play other games
 
 
-def stream_of(data):
-    return (np.stack([d[0] for d in data]), np.stack([d[1] for d in data]), np.array([d[2] for d in data], dtype=np.float32))
-
-
 def test_other_worker_modes_follow_the_board_class(pkg):
     """The numpy-RNG mode (its host mirror boards draw the random numbers: a mirror on other rules than the engine's would
     leave the games out of step) and the serial SelfPlayWorker in both of its modes."""
@@ -345,12 +254,12 @@ def test_other_worker_modes_follow_the_board_class(pkg):
     np.random.seed(11)
     w = pkg.ParallelSelfPlayWorker(pkg.StandardOthelloBitboard, net, num_simulations=6, temperature_threshold=8,
                                    num_parallel_games=4, verbose=False, rng_mode="numpy")
-    check_stream(8, *stream_of(w.execute_episodes(4, add_dirichlet_noise=True)), 4)
+    check_stream(8, "othello", *stream_of(w.execute_episodes(4, add_dirichlet_noise=True)), 4)
     mcts = pkg.MCTS(net)
     for mode, games in (("device", 5), ("numpy", 1)):
         sw = pkg.SelfPlayWorker(pkg.StandardOthelloBitboard, mcts, num_simulations=6, temperature_threshold=8, rng_mode=mode)
         assert sw.rules == "othello"
-        check_stream(8, *stream_of(sw.execute_episodes(games)), games)
+        check_stream(8, "othello", *stream_of(sw.execute_episodes(games)), games)
     assert sw._engine is None and {k[2] for k in mcts._engines} == {"othello"}
 
 
@@ -363,59 +272,23 @@ def test_selfplay_engine_6x6_on_standard_rules(pkg):
     n = eng.selfplay_run(12, 31)
     st, pi, z, gl = eng.selfplay_fetch(n)
     assert n == gl.sum() and 20 <= gl.min() and gl.max() <= 40
-    check_stream(6, st, pi, z, 12, gl)
+    check_stream(6, "othello", st, pi, z, 12, gl)
     n2 = eng.selfplay_run(12, 31)
     for a, b in zip(eng.selfplay_fetch(n2), (st, pi, z, gl)):
         assert np.array_equal(a, b)
 
 
 # ---- 6. lock-step exactness ----------------------------------------------------------------------------------------
-def hip_eval_fn(ev, cap, bs):
-    """eval_fn of py_search whose answers are the HIP network's own: one position in a launch of `cap` rows (the shape the
-    engine launches), priors through oth_policy_exp (the engine's expf).  Memoised per position."""
-    memo = {}
-
-    def fn(s, o, lg):
-        if (s, o) not in memo:
-            ss, oo, ll = (np.zeros(cap, dtype=U64) for _ in range(3))
-            ss[0], oo[0], ll[0] = s, o, lg
-            logp, v = ev.forward_bits(dev_u64(ss), dev_u64(oo), dev_u64(ll))
-            memo[(s, o)] = (ev.policy_probs(logp)[0].cpu().numpy(), float(v[0, 0].cpu()))
-        return memo[(s, o)]
-    return fn
-
-
 def test_lockstep_selfplay_pi_equals_the_python_search(pkg):
     torch.manual_seed(8)
     net = pkg.OthelloResNet(2, 16).eval()
     ev = pkg.HipResNetEvaluator(net)
     sims, games = 6, 4
     eng = pkg.SearchEngine(games, sims, temperature_threshold=8, evaluator=ev, rules="othello")
-    rules = sr.RayRules(8)
-    fn = hip_eval_fn(ev, games, 8)
-    pos = [sr.start_position(8)] * games
-    over = [False] * games                               # (a standard game can end early; none is expected to in 12 plies)
-    plies = [0] * games
-    rng = np.random.Generator(np.random.PCG64(2))
-    eng.selfplay_begin(games)
-    for ply in range(12):
-        pi, active = eng.selfplay_search()
-        assert active.tolist() == [0 if f else 1 for f in over]
-        actions = np.zeros(games, dtype=np.int32)
-        for i, (s, o) in enumerate(pos):
-            if over[i]:
-                continue
-            _, _, _, want = sr.py_search(rules, s, o, sims, 1.0, fn)
-            assert np.array_equal(pi[i], want), "game %d ply %d" % (i, ply)
-            moves = np.flatnonzero(pi[i] > 0)            # different games take different lines
-            a = int(moves[int(rng.integers(len(moves)))])
-            assert a in sr.legal_actions(rules, s, o)
-            actions[i], plies[i] = a, plies[i] + 1
-            pos[i] = s, o = sr.apply_move(rules, s, o, a)
-            over[i] = rules.legal(s, o) == 0 and rules.legal(o, s) == 0
-        assert eng.selfplay_apply(actions) == over.count(False)
-    n = eng.selfplay_end()
-    st, p, z, gl = eng.selfplay_fetch(n)
+    rules = sr.rules_obj(8, "othello")
+    choose = pi_checked_move(rules, sims, hip_eval_fn(ev, games, 8), "reference", np.random.Generator(np.random.PCG64(2)))
+    got = lockstep_selfplay(eng, rules, games, 12, choose)     # (a standard game can end early; none is expected to in 12 plies)
+    plies, over, gl, n = got["plies"], got["over"], got["gl"], got["n"]
     # (a lock-step run harvests the games that ENDED; the ones still in progress have length 0 and no tuples)
     assert sum(plies) > 40 and gl.tolist() == [p_ if f else 0 for p_, f in zip(plies, over)] and n == int(gl.sum())
 

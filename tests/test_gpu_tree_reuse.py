@@ -10,7 +10,7 @@ import torch
 import az_search_ref as az
 import reuse_search_ref as rr
 import std_rules_ref as sr
-from test_gpu_az_search import bits_of, check_stream_az, hip_eval_fn
+from gpu_support import bits_of, check_stream, hip_eval_fn, lockstep_selfplay
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
@@ -110,49 +110,33 @@ def lockstep_games(pkg, ev, sims, games, tree_reuse, script=None):
     searches = [rr.ReuseSearch(rules, sims, 1.0, fn) for _ in range(games)]
     for rs in searches:
         rs.begin(*sr.start_position(8))
-    over, plies = [False] * games, [0] * games
     rng = np.random.Generator(np.random.PCG64(2))
-    played, new_total, unvisited = [], 0, 0
-    eng.selfplay_begin(games)
-    for ply in range(128):
-        if all(over):
-            break
-        pi, active = eng.selfplay_search()
-        assert active.tolist() == [0 if f else 1 for f in over]
-        actions = np.zeros(games, dtype=np.int32)
-        for i, rs in enumerate(searches):
-            if over[i]:
-                continue
-            if script is None:
-                new_total += rs.top_up()[1]
-                assert np.array_equal(pi[i], rs.results()[3]), "game %d ply %d" % (i, ply)
-                legal = sr.legal_actions(rules, *rs.pos)
-                cold = [m for m in legal if pi[i][m] == 0]
-                moves = (cold or legal) if ply % 3 == 2 else np.flatnonzero(pi[i] > 0)
-                a = int(moves[int(rng.integers(len(moves)))])
-                unvisited += pi[i][a] == 0
-            else:
-                a = int(script[ply][i])
-            actions[i], plies[i] = a, plies[i] + 1
-            if script is None:
-                over[i] = rs.advance(a) == "over"
-            else:
-                rs.pos = sr.apply_move(rules, *rs.pos, a)
-                over[i] = rules.legal(*rs.pos) == 0 and rules.legal(rs.pos[1], rs.pos[0]) == 0
-        played.append(actions.copy())
-        assert eng.selfplay_apply(actions) == over.count(False)
-    assert all(over)
-    n = eng.selfplay_end()
-    st, p, z, gl = eng.selfplay_fetch(n)
-    assert gl.tolist() == plies and n == sum(plies)
-    return dict(tuples=(st, p, z), gl=gl, actions=played, new=new_total, unvisited=unvisited, counters=eng.counters(),
-                reuse=eng.reuse_stats())
+    count = dict(new=0, unvisited=0)
+
+    def choose(i, ply, s, o, pi):
+        if script is not None:
+            return int(script[ply][i])
+        rs = searches[i]
+        assert rs.pos == (s, o)
+        count["new"] += rs.top_up()[1]
+        assert np.array_equal(pi, rs.results()[3]), "game %d ply %d" % (i, ply)
+        legal = sr.legal_actions(rules, s, o)
+        cold = [m for m in legal if pi[m] == 0]
+        moves = (cold or legal) if ply % 3 == 2 else np.flatnonzero(pi > 0)
+        a = int(moves[int(rng.integers(len(moves)))])
+        count["unvisited"] += pi[a] == 0
+        rs.advance(a)
+        return a
+    got = lockstep_selfplay(eng, rules, games, 128, choose)
+    assert all(got["over"])
+    assert got["gl"].tolist() == got["plies"] and got["n"] == sum(got["plies"])
+    return dict(got, new=count["new"], unvisited=count["unvisited"], counters=eng.counters(), reuse=eng.reuse_stats())
 
 
 @pytest.mark.parametrize("sims", [6, 24])
 def test_lockstep_selfplay_with_reuse_equals_the_definition(pkg, sims):
     """pi per ply is the definition's, bit for bit, over whole games whose forced actions include unvisited moves; z and
-    the stream's shape go through check_stream_az (which links consecutive positions by a move of positive pi: the forced
+    the stream's shape go through check_stream (which links consecutive positions by a move of positive pi: the forced
     unvisited moves are marked in a COPY of pi with 1e-9, below its 1e-6 bound on the sum); counter [1] is the definition's
     number of new simulations; evaluations fall below the same games without reuse."""
     torch.manual_seed(8)
@@ -176,7 +160,7 @@ def test_lockstep_selfplay_with_reuse_equals_the_definition(pkg, sims):
             if marked[t, a] == 0:
                 marked[t, a] = 1e-9
             t += 1
-    check_stream_az(8, "othello", st, marked, z, games, got["gl"])
+    check_stream(8, "othello", st, marked, z, games, got["gl"], z="alphazero")
     assert got["counters"]["simulations"] == got["new"] < got["counters"]["plies"] * sims
     assert got["reuse"]["inherited_roots"] >= 1
     plain = lockstep_games(pkg, ev, sims, games, False, script=got["actions"])
@@ -375,7 +359,7 @@ def test_noisy_selfplay_with_reuse_is_reproducible(pkg):
     for a, b in zip(noisy, again):
         assert np.array_equal(a, b)
     assert not (noisy[1].shape == plain[1].shape and np.array_equal(noisy[1], plain[1]))
-    check_stream_az(8, "othello", *noisy[:3], 8, noisy[3])
+    check_stream(8, "othello", *noisy[:3], 8, noisy[3], z="alphazero")
     cached = run(True, eval_cache_log2=4)            # the cache is upstream of the tree: the same tuples
     for a, b in zip(cached, noisy):
         assert np.array_equal(a, b)

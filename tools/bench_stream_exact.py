@@ -34,7 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import othello_reinforcement_learning_test_amd as pkg     # noqa: E402
-from test_gpu_selfplay_exact import simulate_stream      # noqa: E402  (the schedule restated on the host)
+from gpu_support import simulate_stream                 # noqa: E402  (the schedule restated on the host)
 
 LEGS = {   # bench.py's `legs` tuple (bench.py: run_leg arguments), one checked step each
     "headline": dict(board=8, blocks=10, filters=128, sims=50, c_puct=1.0, threshold=15, lanes=2, slots=4096, stagger=61,
